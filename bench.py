@@ -12,6 +12,13 @@ One "step" = forward of a1-a16 (stereo cost volume -> MIE -> lift/splat -> 3-D e
 4 losses) + backward, on one seeded synthetic SemanticKITTI-shaped batch per GPU, inputs resident
 in HBM.  N > 1 shards the batch (B per GPU fixed = weak scaling) and adds the gradient exchange
 over RCCL/xGMI (flat buckets overlapped with backward, stereoscene_amd/dp.py).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (`metric`, `value`, `unit`, `ms_per_step`, ...); nothing
+else runs and nothing instruments the timed steps.  ``--full`` adds what takes measurements of its own: HIP events around the
+dominant kernels inside the timed region (`roofline`, `step_roofline`), the forward-only figure, the serial replay, the one-rank
+RCCL process group at N = 1 and the gradient-exchange timings, and the CPU baseline; its complete record goes to
+bench_detail.json.  ``--dump-outputs DIR`` writes what the last timed step returned (losses, a seeded sample of the parameter
+gradients) as float32 .npy files, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -178,7 +185,7 @@ def csrc_sha16():
     return h.hexdigest()[:16]
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -202,7 +209,14 @@ def parse():
     ap.add_argument("--selftest-launcher", action="store_true",
                     help="CPU / gloo dry run of the N-rank launcher, timing protocol and gradient exchange on a toy "
                          "parameter set (tests/test_bench_launcher.py); measures nothing about the HIP path")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: per-kernel HIP events in the timed region (roofline, "
+                         "step_roofline), forward-only figure, serial replay, one-rank RCCL group + gradient exchange, CPU "
+                         "baseline; complete record in bench_detail.json.  --cpu-sample, --skip-* and --no-rccl-world1 tune it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (losses, a seeded sample of the parameter "
+                         "gradients) as DIR/<name>.npy, float32")
+    return ap.parse_args(argv)
 
 
 def _free_port():
@@ -370,6 +384,48 @@ def selftest_launcher(args):
         dist.destroy_process_group()
 
 
+DUMP_GRAD_SAMPLE = 1 << 22          # gradient elements written by --dump-outputs: 16 MB of float32
+
+
+def dump_outputs(dirname, losses, model, sample=DUMP_GRAD_SAMPLE):
+    """--dump-outputs: what one step hands its caller, as float32 .npy files in `dirname`.  `<key>.npy` (0-d) per entry of
+    the losses dict; `grad_sample.npy`: the gradients of model.named_parameters(), flattened and concatenated in that order --
+    all of them if there are at most `sample` elements, else `sample` elements at sorted indices drawn by a generator seeded
+    with 0 (the same indices for every run of the same model)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in losses.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), v.detach().float().cpu().numpy())
+    grads = [p.grad.reshape(-1) for _, p in model.named_parameters() if p.grad is not None]
+    if grads:
+        flat = torch.cat(grads).float()
+        if flat.numel() > sample:
+            idx = torch.randint(flat.numel(), (sample,), generator=torch.Generator().manual_seed(0)).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(dirname, "grad_sample.npy"), flat.cpu().numpy())
+
+
+def headline_record(args, model, world, value, ms, losses):
+    """The contract keys of the result line (what a plain run prints)."""
+    return {"metric": "voxels/sec fwd+bwd, 256x256x32 grid D=192" if args.config == "kitti_d192" else
+            f"voxels/sec fwd+bwd ({args.config})",
+            "value": value, "unit": "voxels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32" if args.precision == "fp32" else ("bf16 (bf16 activations and activation gradients in HBM, bf16 MFMA with fp32 "
+                                                             "accumulation; fp32 master weights, weight gradients, norm statistics, "
+                                                             "softmaxes, scatter and losses)" if args.precision == "bf16" else
+                                                             "bf16 operands (fp32 tensors in HBM; the rounds 1-3 mode)"),
+            "data": "synthetic",
+            "config": {"workload": f"{args.config}: stereo pair features 2x[B,640,48,160] -> 256x256x32 occupancy, "
+                                   f"D={model.img_view_transformer.D}, fwd+bwd incl. 4 losses"
+                                   + (" (forward only)" if args.forward_only else "")
+                                   + (f" (ablation: {args.ablation})" if args.ablation != "full" else "")
+                                   + (" (precision: bf16 mixed, configs[3])" if args.precision != "fp32" else ""),
+                       "batch_per_gpu": args.batch, "global_batch": world * args.batch,
+                       "parallelism": f"dp{world}", "train_mode": True},
+            "losses": {k: float(v.detach()) for k, v in losses.items()}}
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -395,10 +451,10 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", rank=rank, world_size=world,       # RCCL on ROCm
                                 device_id=torch.device("cuda", local))
-    elif world == 1 and not args.forward_only and not args.no_rccl_world1:
-        # N = 1 as the driver runs it (no launcher): a one-rank RCCL process group, so that the step measured here is the step
-        # of the N > 1 runs call for call -- bucket pack, reduce_scatter_tensor(AVG) + all_gather_into_tensor per bucket from
-        # the autograd hooks, wait in finish() -- and the barrier of the timing protocol is RCCL's
+    elif world == 1 and args.full and not args.forward_only and not args.no_rccl_world1:
+        # --full at N = 1 (no launcher): a one-rank RCCL process group, so that the exchange calls of the N > 1 step are timed
+        # after the step (gradient_exchange) and the barrier of the timing protocol is RCCL's.  A one-rank
+        # group exchanges nothing inside the step (dp.py), so a plain run, which times the step alone, does without it
         try:
             os.environ["MASTER_ADDR"] = "127.0.0.1"
             os.environ["MASTER_PORT"] = str(_free_port())
@@ -444,7 +500,7 @@ def main():
     fams = set(SINGLE_KERNEL_FAMILIES)
     if os.environ.get("SSBEV_TIME_FAMILIES"):
         fams |= set(os.environ["SSBEV_TIME_FAMILIES"].split(","))
-    timer = F.KernelTimer(families=fams)
+    timer = F.KernelTimer(families=fams) if args.full else None       # a plain run times the step without events
     F.KERNEL_TIMER = None if os.environ.get('SSBEV_NO_TIMER') else timer
     fence()
     t0 = time.perf_counter()
@@ -460,10 +516,12 @@ def main():
     ms = dt / args.steps * 1e3
     scale = VOXELS_PER_SAMPLE if cfg["occ_size"] == (256, 256, 32) else cfg["occ_size"][0] * cfg["occ_size"][1] * cfg["occ_size"][2]
     value = world * args.batch * scale / (dt / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses, model)
 
     # secondary figure (north_star states its >= 10x-over-CPU target for the FORWARD pass): same model and inputs, no_grad
     fo_ms = None
-    if not args.forward_only and not args.skip_forward_extra:
+    if args.full and not args.forward_only and not args.skip_forward_extra:
         with torch.no_grad():
             for _ in range(min(args.warmup, 2)):
                 model.forward_train(img_inputs=inputs, gt_occ=gt_occ)
@@ -484,7 +542,7 @@ def main():
     from stereoscene_amd import streams as _streams
     from stereoscene_amd.plugin import view_transformer as _vtm
     concurrent = bool(_streams.WGRAD_STREAM or _vtm.VT_STREAMS)
-    if concurrent and not args.forward_only and not args.skip_serial_replay:
+    if args.full and concurrent and not args.forward_only and not args.skip_serial_replay:
         saved = (_streams.WGRAD_STREAM, _vtm.VT_STREAMS)
         _streams.WGRAD_STREAM = _vtm.VT_STREAMS = False
         try:
@@ -505,7 +563,7 @@ def main():
             F.KERNEL_TIMER = None
 
     exch = None
-    if distributed and reducer is not None and (reducer.active or world == 1):
+    if args.full and distributed and reducer is not None and (reducer.active or world == 1):
         exch = exchange_microbench(reducer, dist)
         exch["mode_in_step"] = reducer.exchange if reducer.active else "none (one rank)"
         exch["bytes_per_step_per_rank"] = reducer.flat.numel() * 4
@@ -522,7 +580,11 @@ def main():
     elif rccl_world1 and rccl_world1 != "ok":
         exch = {"world": 1, "rccl_process_group": rccl_world1}
 
-    if rank == 0:
+    if rank == 0 and not args.full:
+        out = headline_record(args, model, world, value, ms, losses)
+        out["detail_file"] = None
+        os.write(json_fd, (compact_record(out) + "\n").encode())
+    elif rank == 0:
         ks = timer.summary()
         peak = PEAK_FP32_MFMA_TFLOPS if args.precision == "fp32" else PEAK_BF16_MFMA_TFLOPS
         # ---- roofline: the dominant SINGLE kernel of the step (largest summed duration among the timed kernels)
@@ -640,27 +702,11 @@ def main():
                      "floor_ms": floor_ex * 1e3 / args.steps, "frac": floor_ex * 1e3 / args.steps / ms,
                      "operator_floor_ms": floor_op * 1e3 / args.steps, "operator_frac": floor_op * 1e3 / args.steps / ms,
                      "groups": groups}
-        out = {"metric": "voxels/sec fwd+bwd, 256x256x32 grid D=192" if args.config == "kitti_d192" else
-               f"voxels/sec fwd+bwd ({args.config})",
-               "value": value, "unit": "voxels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-               "dtype": "f32" if args.precision == "fp32" else ("bf16 (bf16 activations and activation gradients in HBM, bf16 MFMA with fp32 "
-                                                                "accumulation; fp32 master weights, weight gradients, norm statistics, "
-                                                                "softmaxes, scatter and losses)" if args.precision == "bf16" else
-                                                                "bf16 operands (fp32 tensors in HBM; the rounds 1-3 mode)"),
-               "data": "synthetic",
-               "config": {"workload": f"{args.config}: stereo pair features 2x[B,640,48,160] -> 256x256x32 occupancy, "
-                                      f"D={model.img_view_transformer.D}, fwd+bwd incl. 4 losses"
-                                      + (" (forward only)" if args.forward_only else "")
-                                      + (f" (ablation: {args.ablation})" if args.ablation != "full" else "")
-                                      + (" (precision: bf16 mixed, configs[3])" if args.precision != "fp32" else ""),
-                          "batch_per_gpu": args.batch, "global_batch": world * args.batch,
-                          "parallelism": f"dp{world}", "train_mode": True},
-               "roofline": roof, "roofline_other_timed_kernels": roof_other, "roofline_serial_replay": roof_replay,
-               "streams": {"side_stream_weight_gradients": bool(_streams.WGRAD_STREAM), "side_stream_depthnet": bool(_vtm.VT_STREAMS),
-                           "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES")},
-               "step_roofline": step_roof,
-               "losses": {k: float(v.detach()) for k, v in losses.items()}}
+        out = headline_record(args, model, world, value, ms, losses)
+        out.update({"roofline": roof, "roofline_other_timed_kernels": roof_other, "roofline_serial_replay": roof_replay,
+                    "streams": {"side_stream_weight_gradients": bool(_streams.WGRAD_STREAM), "side_stream_depthnet": bool(_vtm.VT_STREAMS),
+                                "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES")},
+                    "step_roofline": step_roof})
         if fo_ms is not None:
             out["forward_only"] = {"ms_per_step": fo_ms, "value": world * args.batch * scale / (fo_ms * 1e-3), "unit": "voxels/s",
                                    "note": "same model / inputs under no_grad, timed after the fwd+bwd region; not the metric"}

@@ -34,6 +34,26 @@ def load_golden(name):
         return {k: z[k] for k in z.files}
 
 
+def reference_config():
+    """The reference's projects/configs/occupancy/semantickitti/stereoscene.py, _base_ files merged, as the values stored in
+    tests/golden/stereoscene_config.json (oracle/make_golden_config.py), in the product's Config; the plugin registries are
+    filled as Config.fromfile does for a config with `plugin = True`."""
+    import importlib
+    import json
+    from stereoscene_amd.registry import Config
+
+    def decode(v):
+        if isinstance(v, dict):
+            return tuple(decode(x) for x in v["__tuple__"]) if set(v) == {"__tuple__"} else {k: decode(x) for k, x in v.items()}
+        return [decode(x) for x in v] if isinstance(v, list) else v
+    with open(os.path.join(GOLDEN, "stereoscene_config.json")) as f:
+        g = json.load(f)
+    cfg = Config(decode(g["config"]), filename=g["source"])
+    if cfg.get("plugin", False):
+        importlib.import_module("stereoscene_amd.plugin")
+    return cfg
+
+
 def state_dict_from_manifest(g, prefix_filter=""):
     """Rebuild a reference state dict from 'shape:<key>' manifest entries with the fill-by-key rule."""
     from stereoscene_amd import synthetic as S

@@ -146,7 +146,7 @@ def test_bench_two_ranks_prints_one_record_with_bus_bandwidth():
     """bench.py exactly as the driver launches it at N = 2 (torch.distributed.run, one rank per GPU over RCCL), small config."""
     import json
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = _launch_two_ranks([os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "small_d48",
+    out = _launch_two_ranks([os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "small_d48",
                              "--cpu-sample", "none", "--skip-serial-replay"])
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

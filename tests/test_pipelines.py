@@ -396,13 +396,11 @@ def test_training_loop_from_files_with_runner(tmp_path):
     assert [h["epoch"] for h in hist2] == [5] and np.isfinite(sum(v for k, v in hist2[0].items() if k.startswith("loss")))
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/projects/configs/occupancy/semantickitti/stereoscene.py"),
-                    reason="reference checkout not present (GPU box)")
 def test_reference_config_pipelines_build_unchanged():
     """train_pipeline / test_pipeline / data.train of the reference's own config build from the registries as they are
     (host logic: no file is read, no kernel launched)."""
-    from stereoscene_amd.registry import Config
-    cfg = Config.fromfile("/root/reference/projects/configs/occupancy/semantickitti/stereoscene.py")
+    from conftest import reference_config
+    cfg = reference_config()
     train = P.Compose(cfg.train_pipeline)
     test = P.Compose(cfg.test_pipeline)
     assert [type(s).__name__ for s in train.steps] == ["LoadMultiViewImageFromFiles_SemanticKitti", "LoadSemKittiAnnotation",

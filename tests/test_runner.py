@@ -74,12 +74,8 @@ def test_runner_hooks_checkpoint_rotation_best_and_resume(tmp_path):
 
 
 def test_runner_kwargs_from_the_reference_config():
-    import pytest
-    from stereoscene_amd.registry import Config
-    path = "/root/reference/projects/configs/occupancy/semantickitti/stereoscene.py"
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present (GPU box)")
-    cfg = Config.fromfile(path)
+    from conftest import reference_config
+    cfg = reference_config()
     kw = R.runner_kwargs_from_config(cfg)
     assert kw == dict(base_lr=1e-4, lr_step=(20, 25), lr_gamma=0.1, max_epochs=30, ckpt_interval=1, max_keep_ckpts=2,
                       eval_interval=2, save_best="semkitti_combined_IoU", rule="greater")

@@ -7,9 +7,9 @@ out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.txt 2>&1; echo "smoke rc=$?" >> $out/smoke.txt
-SSBEV_BENCH_DETAIL=$out/bench_detail.json timeout 900 python bench.py > $out/bench_line.json 2> $out/bench.err
-timeout 300 python bench.py --steps 10 --warmup 5 --cpu-sample none --precision bf16 2>/dev/null | tail -1 > $out/bench_line_bf16.json
-timeout 300 python bench.py --steps 8 --warmup 5 --cpu-sample none --precision bf16 --batch 2 --skip-forward-extra 2>/dev/null | tail -1 > $out/bench_line_bf16_b2.json
+SSBEV_BENCH_DETAIL=$out/bench_detail.json timeout 900 python bench.py --full > $out/bench_line.json 2> $out/bench.err
+timeout 300 python bench.py --full --steps 10 --warmup 5 --cpu-sample none --precision bf16 2>/dev/null | tail -1 > $out/bench_line_bf16.json
+timeout 300 python bench.py --full --steps 8 --warmup 5 --cpu-sample none --precision bf16 --batch 2 --skip-forward-extra 2>/dev/null | tail -1 > $out/bench_line_bf16_b2.json
 # bf16 storage mode (configs[3]): serial-schedule kernel roll-up at B = 2, layer table at B = 1, PMC traffic of its kernels at B = 1
 SSBEV_WGRAD_STREAM=0 SSBEV_VT_STREAMS=0 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/profb_$tag -o k -- python bench.py --steps 6 --warmup 6 --cpu-sample none --skip-forward-extra --skip-serial-replay --precision bf16 --batch 2 > /dev/null 2>&1
 cp $(find /tmp/profb_$tag -name "*kernel_stats.csv" | head -1) $out/kernel_stats_bf16_b2_serial.csv
@@ -56,7 +56,7 @@ res = {}
 for mode in ("full", "stereo_only", "bev_only"):
     import os
     env = dict(os.environ, SSBEV_BENCH_DETAIL="/tmp/ablation_detail.json")
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "8", "--warmup", "3", "--cpu-sample", "none", "--skip-forward-extra",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "8", "--warmup", "3", "--cpu-sample", "none", "--skip-forward-extra",
                           "--skip-serial-replay", "--ablation", mode], capture_output=True, text=True, timeout=600, env=env).stdout.strip().splitlines()[-1]
     d = json.loads(out)
     sr = json.load(open("/tmp/ablation_detail.json"))["step_roofline"]      # the per-group table lives in the detail file
