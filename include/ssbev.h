@@ -460,6 +460,15 @@ int ssbev_resize_pil_u8(const uint8_t* src, int Hs, int Ws, int C, const int32_t
                         ssbev_stream_t stream);
 int ssbev_crop_normalize_u8(const uint8_t* src, int Hs, int Ws, float* dst, int x0, int y0, int w, int h, int flip,
                             const float* mean, const float* stdinv, int swap_rb, ssbev_stream_t stream);
+/* ssbev_crop_rotate_normalize_u8 (since version 101): the same crop + flip + normalise followed by Pillow's `img.rotate(rotate)`
+ * (loading_semkitti.py:128-135: nearest neighbour, expand=False, centre (w/2, h/2) of the cropped image, black fill), byte-exact
+ * with Pillow in its 16.16 fixed-point range.  affine6 = libImaging's fixed-point inverse map a0..a5 (HOST pointer, 6 int32;
+ * pipelines.pil_rotate_fixed): output (x, y) takes intermediate pixel xi = (a2 + y*a1 + x*a0) >> 16, yi = (a5 + y*a4 + x*a3) >> 16
+ * (floor), 0 when (xi, yi) lies outside [0,w) x [0,h); otherwise it reads src[y0+yi][x0+xi'] with xi' = w-1-xi when flip, 0
+ * outside the source, and normalises as ssbev_crop_normalize_u8. */
+int ssbev_crop_rotate_normalize_u8(const uint8_t* src, int Hs, int Ws, float* dst, int x0, int y0, int w, int h, int flip,
+                                   const int32_t* affine6, const float* mean, const float* stdinv, int swap_rb,
+                                   ssbev_stream_t stream);
 /* Depth BCE loss (ViewTransformerLSSVoxel.py:349-416: get_downsampled_gt_depth + get_depth_loss): gt_depths [BN, fH*ds, fW*ds]
  * (0 = no LiDAR return), depth_pred [BN, D, fH, fW] (a probability distribution over the D bins per pixel).  out2[0] = weight *
  * sum of the binary cross entropies over the pixels that have a return / max(their number, 1), out2[1] = that divisor.  The

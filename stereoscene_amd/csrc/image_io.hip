@@ -68,6 +68,32 @@ crop_normalize_kernel(const unsigned char* __restrict__ src, float* __restrict__
   }
 }
 
+struct RotParams { NormParams n; long long a[6]; };
+
+// Pillow's `img.rotate(angle)` (nearest, expand=False, black fill) of the cropped + flipped w x h image, fused with the crop /
+// flip / normalise above: output (x, y) reads intermediate pixel (xi, yi) = ((a2 + y a1 + x a0) >> 16, (a5 + y a4 + x a3) >> 16)
+// (libImaging Geometry.c `affine_fixed`: 16.16 fixed point, arithmetic shift = floor); 0 outside [0,w) x [0,h) (rotate fill),
+// then the same read and normalise as crop_normalize_kernel (0 outside the source = crop fill).
+__global__ void __launch_bounds__(256)
+crop_rotate_normalize_kernel(const unsigned char* __restrict__ src, float* __restrict__ dst, RotParams r, int Hs, int Ws, int h,
+                             int w) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)h * w) return;
+  const int x = (int)(i % w), y = (int)(i / w);
+  const long long xx = r.a[2] + y * r.a[1] + x * r.a[0], yy = r.a[5] + y * r.a[4] + x * r.a[3];
+  const long long xi = xx >> 16, yi = yy >> 16;
+  const NormParams& p = r.n;
+  bool in = xi >= 0 && xi < w && yi >= 0 && yi < h;
+  const int sx = in ? p.x0 + (p.flip ? w - 1 - (int)xi : (int)xi) : 0, sy = in ? p.y0 + (int)yi : 0;
+  in = in && sx >= 0 && sx < Ws && sy >= 0 && sy < Hs;
+  const unsigned char* px = src + ((long)sy * Ws + sx) * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float v = in ? (float)px[p.swap_rb ? 2 - c : c] : 0.0f;
+    dst[(long)c * h * w + i] = (v - p.mean[c]) * p.stdinv[c];
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -103,6 +129,19 @@ int ssbev_crop_normalize_u8(const uint8_t* src, int Hs, int Ws, float* dst, int 
   p.x0 = x0; p.y0 = y0; p.flip = flip ? 1 : 0; p.swap_rb = swap_rb ? 1 : 0;
   hipLaunchKernelGGL(crop_normalize_kernel, dim3(cdiv((size_t)h * w, 256)), dim3(256), 0, as_stream(stream), src, dst, p, Hs, Ws,
                      h, w);
+  return ssbev_launch_status();
+}
+
+int ssbev_crop_rotate_normalize_u8(const uint8_t* src, int Hs, int Ws, float* dst, int x0, int y0, int w, int h, int flip,
+                                   const int32_t* affine6, const float* mean, const float* stdinv, int swap_rb,
+                                   ssbev_stream_t stream) {
+  if (!src || !dst || !affine6 || !mean || !stdinv || Hs <= 0 || Ws <= 0 || w <= 0 || h <= 0) return SSBEV_EINVAL;
+  RotParams r;
+  for (int c = 0; c < 3; ++c) { r.n.mean[c] = mean[c]; r.n.stdinv[c] = stdinv[c]; }   // host pointers (3 floats each)
+  for (int k = 0; k < 6; ++k) r.a[k] = affine6[k];                                       // host pointer (6 int32)
+  r.n.x0 = x0; r.n.y0 = y0; r.n.flip = flip ? 1 : 0; r.n.swap_rb = swap_rb ? 1 : 0;
+  hipLaunchKernelGGL(crop_rotate_normalize_kernel, dim3(cdiv((size_t)h * w, 256)), dim3(256), 0, as_stream(stream), src, dst, r,
+                     Hs, Ws, h, w);
   return ssbev_launch_status();
 }
 

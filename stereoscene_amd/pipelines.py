@@ -237,6 +237,48 @@ def crop_normalize(img, crop, flip, mean, std, swap_rb=False):
     return out
 
 
+def pil_rotate_fixed(w, h, angle):
+    """libImaging's 16.16 fixed-point inverse map of ``Image.rotate(angle)`` on a w x h image (nearest, expand=False, centre
+    (w/2, h/2)) -> int32 [6] = a0..a5: output (x, y) reads input ((a2 + y*a1 + x*a0) >> 16, (a5 + y*a4 + x*a3) >> 16).
+    Restates Image.rotate's matrix (Python doubles, entries rounded to 15 digits) and Geometry.c ``affine_fixed``
+    (FIX(v) = floor(v * 65536 + 0.5), the half-pixel offset folded into a2 / a5).  Pillow's 0 / 90 / 180 / 270 shortcuts give
+    the same bytes.  Outside the fixed-point range (``check_fixed`` at the four corners) Pillow switches to a double-precision
+    loop that is not restated here: refused."""
+    m = [0.0] * 6
+    a = -math.radians(angle % 360.0)
+    m[0], m[1], m[3], m[4] = round(math.cos(a), 15), round(math.sin(a), 15), round(-math.sin(a), 15), round(math.cos(a), 15)
+    cx, cy = w / 2.0, h / 2.0
+    m[2] = m[0] * -cx + m[1] * -cy + m[2] + cx
+    m[5] = m[3] * -cx + m[4] * -cy + m[5] + cy
+    for x, y in ((0, 0), (w, h), (0, h), (w, 0)):
+        if not (abs(x * m[0] + y * m[1] + m[2] + 0.5) < 32768.0 and abs(x * m[3] + y * m[4] + m[5] + 0.5) < 32768.0):
+            raise NotImplementedError(f"rotate of a {w}x{h} image by {angle} deg leaves Pillow's 16.16 fixed-point range; its "
+                                      "double-precision transform is not built")
+
+    def fix(v):
+        return math.floor(v * 65536.0 + 0.5)
+    return np.array([fix(m[0]), fix(m[1]), fix(m[2] + m[1] * 0.5 + m[0] * 0.5), fix(m[3]), fix(m[4]),
+                     fix(m[5] + m[4] * 0.5 + m[3] * 0.5)], dtype=np.int32)
+
+
+def crop_rotate_normalize(img, crop, flip, rotate, mean, std, swap_rb=False):
+    """``crop_normalize`` with ``img.rotate(rotate)`` (Pillow defaults) between the flip and the normalisation, in one pass:
+    uint8 [H, W, 3] -> float32 [3, h, w], byte-exact with Pillow (tests/test_gpu_image_augment.py)."""
+    lib = capi.load()
+    Hs, Ws, _ = img.shape
+    x0, y0, x1, y1 = (int(v) for v in crop)
+    w, h = x1 - x0, y1 - y0
+    affine = pil_rotate_fixed(w, h, rotate)
+    out = torch.empty(3, h, w, dtype=torch.float32, device=img.device)
+    m = np.asarray(mean, dtype=np.float32)
+    si = (1.0 / np.asarray(std, dtype=np.float32).astype(np.float64)).astype(np.float32)
+    capi.check(lib.ssbev_crop_rotate_normalize_u8(capi.ptr(img.contiguous()), Hs, Ws, capi.ptr(out), x0, y0, w, h, int(bool(flip)),
+                                                  affine.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p),
+                                                  si.ctypes.data_as(C.c_void_p), int(bool(swap_rb)), capi.stream()),
+               "ssbev_crop_rotate_normalize_u8")
+    return out
+
+
 def read_image_rgb(path):
     """PNG/JPEG -> uint8 [H, W, 3] in RGB order (upstream reads BGR with cv2 and swaps inside imnormalize: same pixels)."""
     from PIL import Image
@@ -247,11 +289,11 @@ def read_image_rgb(path):
 @PIPELINES.register_module()
 class LoadMultiViewImageFromFiles_SemanticKitti:
     """Pipeline step of stereoscene.py:140 (loading_semkitti.py:76-302): loads the stereo pair, applies the image-view
-    augmentation (resize / crop / flip; the same draw for both views), normalises, and assembles
+    augmentation (resize / crop / flip / rotate; the same draw for both views), normalises, and assembles
     ``results['img_inputs'] = [left, right]`` with each view = [img, rot, tran, intrin, post_rot, post_tran, depth,
-    cam2lidar, calib] (leading axis of 1).  Pixels are produced on the GPU (``resize_u8`` / ``crop_normalize``); the
-    augmentation draw and the 3x3 bookkeeping are host code, as upstream.  ``rot != 0`` and ``colorjitter`` are not built
-    (the config sets rot = (0, 0), colorjitter = False)."""
+    cam2lidar, calib] (leading axis of 1).  Pixels are produced on the GPU (``resize_u8``, then ``crop_normalize`` or, for a
+    non-zero angle, ``crop_rotate_normalize``); the augmentation draw and the 3x3 bookkeeping are host code, as upstream.
+    ``colorjitter`` and ``load_depth`` are not built (both off in stereoscene.py)."""
 
     def __init__(self, data_config, is_train=False, colorjitter=False, img_norm_cfg=None, load_depth=False, device="cuda"):
         if colorjitter or load_depth:
@@ -296,10 +338,20 @@ class LoadMultiViewImageFromFiles_SemanticKitti:
         """Affine maps of image coordinates as (M [2,2], t [2]) fp32 pairs: ``step`` applied after ``cur``."""
         return step[0].matmul(cur[0]), step[0].matmul(cur[1]) + step[1]
 
-    def pixel_map(self, post_rot, post_tran, resize, crop, flip):
+    @staticmethod
+    def rotation_step(rotate, crop):
+        """The fourth step of ``pixel_map``: rotation by ``rotate`` degrees about the crop centre, as the reference builds it
+        (loading_semkitti.py:120-123: ``get_rot`` in float64 rounded to fp32, the centre term in fp32)."""
+        h = rotate / 180 * np.pi
+        A = torch.Tensor([[np.cos(h), np.sin(h)], [-np.sin(h), np.cos(h)]])
+        b = torch.Tensor([crop[2] - crop[0], crop[3] - crop[1]]) / 2
+        return A, A.matmul(-b) + b
+
+    def pixel_map(self, post_rot, post_tran, resize, crop, flip, rotate=0):
         """The pixel map raw image -> network input composed onto (post_rot, post_tran): scale, shift by the crop corner,
-        mirror about the crop width (what the reference accumulates at loading_semkitti.py:109-125; a rotation about the crop
-        centre would be the fourth step).  This is a true composition of affine maps; the reference's in-place update leaves an
+        mirror about the crop width, rotate about the crop centre (what the reference accumulates at
+        loading_semkitti.py:109-125; at angle 0 the reference's rotation step is the identity, so it is composed only for a
+        non-zero angle).  This is a true composition of affine maps; the reference's in-place update leaves an
         incoming translation unscaled (loading_semkitti.py:113-114), and the two agree exactly when the incoming translation is
         zero -- which is the only way the loader calls it (``_view`` passes eye(2) / zeros(2)).  Anything else is refused."""
         if bool((torch.as_tensor(post_tran) != 0).any()):
@@ -310,6 +362,8 @@ class LoadMultiViewImageFromFiles_SemanticKitti:
                  (eye, -torch.Tensor([crop[0], crop[1]]))]
         if flip:
             steps.append((torch.Tensor([[-1, 0], [0, 1]]), torch.Tensor([crop[2] - crop[0], 0])))
+        if rotate != 0:
+            steps.append(self.rotation_step(rotate, crop))
         m = (post_rot, post_tran)
         for step in steps:
             m = self._then(step, m)
@@ -317,11 +371,13 @@ class LoadMultiViewImageFromFiles_SemanticKitti:
 
     def img_transform(self, img, post_rot, post_tran, resize, resize_dims, crop, flip, rotate):
         """img: uint8 [H, W, 3] on the GPU -> normalised float [3, fH, fW] + the updated (post_rot, post_tran)."""
-        if rotate != 0:
-            raise NotImplementedError("image rotation is off in stereoscene.py (rot = (0, 0)) and not built")
         cfg = self.img_norm_cfg or dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
-        out = crop_normalize(resize_u8(img, resize_dims), crop, flip, cfg["mean"], cfg["std"], swap_rb=False)
-        post_rot, post_tran = self.pixel_map(post_rot, post_tran, resize, crop, flip)
+        resized = resize_u8(img, resize_dims)
+        if rotate != 0:
+            out = crop_rotate_normalize(resized, crop, flip, rotate, cfg["mean"], cfg["std"], swap_rb=False)
+        else:
+            out = crop_normalize(resized, crop, flip, cfg["mean"], cfg["std"], swap_rb=False)
+        post_rot, post_tran = self.pixel_map(post_rot, post_tran, resize, crop, flip, rotate)
         return out, post_rot, post_tran
 
     def _view(self, results, k, augs):
