@@ -469,6 +469,27 @@ int ssbev_crop_normalize_u8(const uint8_t* src, int Hs, int Ws, float* dst, int 
 int ssbev_crop_rotate_normalize_u8(const uint8_t* src, int Hs, int Ws, float* dst, int x0, int y0, int w, int h, int flip,
                                    const int32_t* affine6, const float* mean, const float* stdinv, int swap_rb,
                                    ssbev_stream_t stream);
+/* ssbev_crop_rotate_jitter_normalize_u8 (since version 102): ssbev_crop_rotate_normalize_u8 with the train-time colour jitter
+ * (loading_semkitti.py:213, 273: PhotoMetricDistortionMultiViewImage, loading_bevdet.py:532-620) between the rotate and the
+ * normalise; affine6 = pil_rotate_fixed(w, h, 0) is the identity map for an unrotated view.  The pixel as the normalise reads it
+ * (RGB) is the upstream's image in BGR order b = c2, g = c1, r = c0, in fp32, and the drawn values (HOST pointer) apply as:
+ *   1. flags & BRIGHTNESS: x += delta                     2. mode == 1 and flags & CONTRAST: x *= alpha
+ *   3. BGR -> HSV as OpenCV's scalar float path (RGB2HSV_f, h in degrees)
+ *   4. flags & SATURATION: s *= saturation                 5. flags & HUE: h += hue; h > 360: h -= 360; then h < 0: h += 360
+ *   6. HSV -> BGR (HSV2RGB_f)                              7. mode == 0 and flags & CONTRAST: x *= alpha
+ *   8. flags & SWAP: x = x[perm] (perm indexes BGR)        9. uint8 without clipping: truncate toward zero, keep the low 8 bits
+ * every product and sum rounded on its own (no FMA), IEEE division; then the normalise as ssbev_crop_normalize_u8.
+ * SSBEV_EINVAL when perm is not a permutation of {0, 1, 2}, mode is not 0 / 1, flags has unknown bits, or a value is not
+ * finite or outside |delta| <= 255, 0 <= alpha, saturation <= 8, |hue| <= 360 (upstream draws +-32, 0.5..1.5, +-18). */
+#define SSBEV_JITTER_BRIGHTNESS 1
+#define SSBEV_JITTER_CONTRAST 2
+#define SSBEV_JITTER_SATURATION 4
+#define SSBEV_JITTER_HUE 8
+#define SSBEV_JITTER_SWAP 16
+typedef struct { int flags, mode; float delta, alpha, saturation, hue; int perm[3]; } ssbev_jitter_params;
+int ssbev_crop_rotate_jitter_normalize_u8(const uint8_t* src, int Hs, int Ws, float* dst, int x0, int y0, int w, int h, int flip,
+                                          const int32_t* affine6, const ssbev_jitter_params* jitter, const float* mean,
+                                          const float* stdinv, int swap_rb, ssbev_stream_t stream);
 /* Depth BCE loss (ViewTransformerLSSVoxel.py:349-416: get_downsampled_gt_depth + get_depth_loss): gt_depths [BN, fH*ds, fW*ds]
  * (0 = no LiDAR return), depth_pred [BN, D, fH, fW] (a probability distribution over the D bins per pixel).  out2[0] = weight *
  * sum of the binary cross entropies over the pixels that have a return / max(their number, 1), out2[1] = that divisor.  The

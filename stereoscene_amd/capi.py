@@ -95,6 +95,14 @@ class GemmDims(C.Structure):
                 ("ep_mul", C.c_void_p), ("ep_rowsub", C.c_void_p)]
 
 
+class JitterParams(C.Structure):
+    _fields_ = [("flags", C.c_int), ("mode", C.c_int), ("delta", C.c_float), ("alpha", C.c_float), ("saturation", C.c_float),
+                ("hue", C.c_float), ("perm", C.c_int * 3)]
+
+
+JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE, JITTER_SWAP = 1, 2, 4, 8, 16
+
+
 class AdamWCfg(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
                 ("weight_decay", C.c_float), ("max_grad_norm", C.c_float), ("step", C.c_int)]
@@ -164,6 +172,8 @@ SIGNATURES = {
     "ssbev_crop_normalize_u8": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P]),
     "ssbev_crop_rotate_normalize_u8": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P,
                                                 C.c_int, _P]),
+    "ssbev_crop_rotate_jitter_normalize_u8": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P,
+                                                       C.POINTER(JitterParams), _P, _P, C.c_int, _P]),
     "ssbev_depth_bce_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "ssbev_depth_bce_fwd": (C.c_int, [_P, _P, _P] + [C.c_int] * 5 + [C.c_float] * 3 + [_P, C.c_size_t, _P]),
     "ssbev_depth_bce_bwd": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [C.c_float] * 3 + [_P, _P]),

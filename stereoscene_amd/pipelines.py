@@ -279,6 +279,45 @@ def crop_rotate_normalize(img, crop, flip, rotate, mean, std, swap_rb=False):
     return out
 
 
+def jitter_params(jitter):
+    """The drawn colour jitter of one view (``LoadMultiViewImageFromFiles_SemanticKitti.sample_jitter``: a step is on when its
+    value is not None) -> ``capi.JitterParams``; the Python floats are rounded to fp32 here, as numpy rounds them when it
+    applies them to the float32 image."""
+    p = capi.JitterParams(mode=int(jitter["mode"]), delta=0.0, alpha=1.0, saturation=1.0, hue=0.0)
+    for key, bit in (("delta", capi.JITTER_BRIGHTNESS), ("alpha", capi.JITTER_CONTRAST), ("saturation", capi.JITTER_SATURATION),
+                     ("hue", capi.JITTER_HUE)):
+        if jitter[key] is not None:
+            p.flags |= bit
+            setattr(p, key, float(jitter[key]))
+    p.perm[:] = [0, 1, 2] if jitter["perm"] is None else [int(v) for v in jitter["perm"]]
+    if jitter["perm"] is not None:
+        p.flags |= capi.JITTER_SWAP
+    return p
+
+
+def crop_rotate_jitter_normalize(img, crop, flip, rotate, jitter, mean, std, swap_rb=False):
+    """``crop_rotate_normalize`` with the upstream's train-time colour jitter (PhotoMetricDistortionMultiViewImage,
+    loading_bevdet.py:532-620: brightness, contrast, HSV saturation / hue through OpenCV's float conversions, channel swap, an
+    unclipped uint8 cast) between the rotate and the normalisation, in one pass: uint8 [H, W, 3] -> float32 [3, h, w].  ``jitter``
+    is one view's draw (``sample_jitter``); ``rotate`` = 0 reads through the identity map.  Bit-exact with the numpy statement
+    of the upstream (tests/test_gpu_image_jitter.py)."""
+    lib = capi.load()
+    Hs, Ws, _ = img.shape
+    x0, y0, x1, y1 = (int(v) for v in crop)
+    w, h = x1 - x0, y1 - y0
+    affine = pil_rotate_fixed(w, h, rotate)
+    params = jitter_params(jitter)
+    out = torch.empty(3, h, w, dtype=torch.float32, device=img.device)
+    m = np.asarray(mean, dtype=np.float32)
+    si = (1.0 / np.asarray(std, dtype=np.float32).astype(np.float64)).astype(np.float32)
+    capi.check(lib.ssbev_crop_rotate_jitter_normalize_u8(capi.ptr(img.contiguous()), Hs, Ws, capi.ptr(out), x0, y0, w, h,
+                                                         int(bool(flip)), affine.ctypes.data_as(C.c_void_p), C.byref(params),
+                                                         m.ctypes.data_as(C.c_void_p), si.ctypes.data_as(C.c_void_p),
+                                                         int(bool(swap_rb)), capi.stream()),
+               "ssbev_crop_rotate_jitter_normalize_u8")
+    return out
+
+
 def read_image_rgb(path):
     """PNG/JPEG -> uint8 [H, W, 3] in RGB order (upstream reads BGR with cv2 and swaps inside imnormalize: same pixels)."""
     from PIL import Image
@@ -292,13 +331,21 @@ class LoadMultiViewImageFromFiles_SemanticKitti:
     augmentation (resize / crop / flip / rotate; the same draw for both views), normalises, and assembles
     ``results['img_inputs'] = [left, right]`` with each view = [img, rot, tran, intrin, post_rot, post_tran, depth,
     cam2lidar, calib] (leading axis of 1).  Pixels are produced on the GPU (``resize_u8``, then ``crop_normalize`` or, for a
-    non-zero angle, ``crop_rotate_normalize``); the augmentation draw and the 3x3 bookkeeping are host code, as upstream.
-    ``colorjitter`` and ``load_depth`` are not built (both off in stereoscene.py)."""
+    non-zero angle, ``crop_rotate_normalize``; with ``colorjitter`` in training, ``crop_rotate_jitter_normalize``); the
+    augmentation draws and the 3x3 bookkeeping are host code, as upstream.  ``colorjitter`` is refused with
+    ``is_train=False``, where the upstream ignores it.  ``load_depth`` is not built: the upstream's right-view branch calls
+    ``.replace`` on the file-name list (loading_semkitti.py:220) and fails there itself."""
 
     def __init__(self, data_config, is_train=False, colorjitter=False, img_norm_cfg=None, load_depth=False, device="cuda"):
-        if colorjitter or load_depth:
-            raise NotImplementedError("colorjitter / load_depth are off in stereoscene.py and not built")
+        if load_depth:
+            raise NotImplementedError("load_depth is not built: the upstream's own right-view branch fails on it "
+                                      "(loading_semkitti.py:220 calls .replace on the file-name list)")
+        if colorjitter and not is_train:
+            raise NotImplementedError("colorjitter is built for training only (is_train=True): the upstream applies it only "
+                                      "when `colorjitter and is_train` (loading_semkitti.py:213, 273), so in evaluation it "
+                                      "would do nothing; set colorjitter=False there")
         self.is_train, self.data_config, self.img_norm_cfg, self.device = is_train, data_config, img_norm_cfg, device
+        self.colorjitter = colorjitter
 
     # The image-view augmentation of one sample = five numbers (scale, left, top, mirrored, angle).  TRAIN draws them from
     # numpy's global RNG; the fixture tests/golden/image_loading.npz pins the ORDER of the draws and the integer truncations
@@ -332,6 +379,31 @@ class LoadMultiViewImageFromFiles_SemanticKitti:
             left = int(max(0, st["size"][0] - fW) / 2)
             mirrored, angle = (False if flip is None else flip), 0
         return st["scale"], st["size"], (left, top, left + fW, top + fH), mirrored, angle
+
+    # The colour jitter of one view (PhotoMetricDistortionMultiViewImage with its defaults, loading_bevdet.py:532-620), drawn
+    # from numpy's global RNG when ``colorjitter`` and ``is_train``: after the shared draw above, for the right view and then
+    # for the left (loading_semkitti.py:213, 273), nothing otherwise.  Each row is (name, "is its coin flipped?" -- None: the
+    # value is drawn unconditionally, draw); a value is drawn only when its coin comes up 1, so the number of values consumed
+    # varies.  Contrast is drawn before the HSV round trip in mode 1 and after it in mode 0.
+    _JITTER_DRAWS = (
+        ("delta", lambda st: True, lambda: np.random.uniform(-32, 32)),
+        ("mode", None, lambda: int(np.random.randint(2))),
+        ("alpha", lambda st: st["mode"] == 1, lambda: np.random.uniform(0.5, 1.5)),
+        ("saturation", lambda st: True, lambda: np.random.uniform(0.5, 1.5)),
+        ("hue", lambda st: True, lambda: np.random.uniform(-18, 18)),
+        ("alpha", lambda st: st["mode"] == 0, lambda: np.random.uniform(0.5, 1.5)),
+        ("perm", lambda st: True, lambda: tuple(int(v) for v in np.random.permutation(3))),
+    )
+
+    def sample_jitter(self):
+        """-> one view's colour jitter {delta, mode, alpha, saturation, hue, perm}; a step that is off has the value None."""
+        st = dict(delta=None, mode=None, alpha=None, saturation=None, hue=None, perm=None)
+        for name, coin, draw in self._JITTER_DRAWS:
+            if coin is None:
+                st[name] = draw()
+            elif coin(st) and np.random.randint(2):
+                st[name] = draw()
+        return st
 
     @staticmethod
     def _then(step, cur):
@@ -369,11 +441,16 @@ class LoadMultiViewImageFromFiles_SemanticKitti:
             m = self._then(step, m)
         return m
 
-    def img_transform(self, img, post_rot, post_tran, resize, resize_dims, crop, flip, rotate):
-        """img: uint8 [H, W, 3] on the GPU -> normalised float [3, fH, fW] + the updated (post_rot, post_tran)."""
+    def img_transform(self, img, post_rot, post_tran, resize, resize_dims, crop, flip, rotate, jitter=None):
+        """img: uint8 [H, W, 3] on the GPU -> normalised float [3, fH, fW] + the updated (post_rot, post_tran).  ``jitter``:
+        the view's colour jitter (``sample_jitter``), applied after the rotate when ``colorjitter`` and ``is_train``."""
         cfg = self.img_norm_cfg or dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
         resized = resize_u8(img, resize_dims)
-        if rotate != 0:
+        if self.colorjitter and self.is_train:
+            if jitter is None:
+                raise ValueError("colorjitter in training: img_transform needs the view's draw (sample_jitter)")
+            out = crop_rotate_jitter_normalize(resized, crop, flip, rotate, jitter, cfg["mean"], cfg["std"], swap_rb=False)
+        elif rotate != 0:
             out = crop_rotate_normalize(resized, crop, flip, rotate, cfg["mean"], cfg["std"], swap_rb=False)
         else:
             out = crop_normalize(resized, crop, flip, cfg["mean"], cfg["std"], swap_rb=False)
@@ -383,7 +460,9 @@ class LoadMultiViewImageFromFiles_SemanticKitti:
     def _view(self, results, k, augs):
         raw = torch.from_numpy(np.array(read_image_rgb(results["img_filename"][k]))).to(self.device)
         resize, resize_dims, crop, flip, rotate = augs
-        img, post_rot2, post_tran2 = self.img_transform(raw, torch.eye(2), torch.zeros(2), resize, resize_dims, crop, flip, rotate)
+        jitter = self.sample_jitter() if (self.colorjitter and self.is_train) else None
+        img, post_rot2, post_tran2 = self.img_transform(raw, torch.eye(2), torch.zeros(2), resize, resize_dims, crop, flip, rotate,
+                                                        jitter)
         post_tran, post_rot = torch.zeros(3), torch.eye(3)
         post_tran[:2] = post_tran2
         post_rot[:2, :2] = post_rot2
