@@ -404,6 +404,30 @@ int ssbev_occ_loss_bwd(const float* logits, const uint8_t* label, const float* c
                        const float* coef, float* grad_logits, const ssbev_occloss_dims* d, void* ws,
                        size_t ws_bytes, ssbev_stream_t stream);
 
+/* ssbev_occ_predict (since version 103): the INFERENCE epilogue of the head in one pass over the coarse logits -- what the
+ * reference does with F.interpolate (bevdepth_occupancy.py:293), torch.argmax + SSCMetrics (semantic_kitti_lss_dataset.py:
+ * 231-287; apis/test.py:141-224) and the submission writer's argmax + learning_map_inv (apis/test.py:49-64), without the 168 MB
+ * of up-sampled logits.
+ *   logits    [B, D, H, W, 20] fp32 channels-last, 16-byte aligned (d->C must be 20)
+ *   label     [B, 2D, 2H, 2W] uint8, 255 (any value >= 20) = ignore; optional, required by conf / n_ignored
+ *   remap     HOST pointer to 20 uint16 (training id -> raw id, e.g. SemanticKITTI learning_map_inv), copied by the call;
+ *             optional, required by raw
+ *   pred      [B, 2D, 2H, 2W] uint8: argmax over the classes of the x2 trilinear up-sampled logits (align_corners=False); the
+ *             interpolated values are those of ssbev_trilinear2x_fwd bit for bit (same taps, weight product and accumulation
+ *             order) and ties go to the lowest class index, so pred == argmax(ssbev_trilinear2x_fwd(logits)) exactly
+ *   raw       [B, 2D, 2H, 2W] uint16 = remap[pred] (the bytes of a SemanticKITTI .label file)
+ *   conf      [B, 20, 20] int64, [gt][pred], PER SAMPLE, over the voxels whose label is not ignored
+ *   n_ignored [B] int64: ignored voxels per sample
+ * Every output is optional (NULL), at least one must be given.  Counts are integer sums (LDS atomics, per-block partials, one
+ * reduce): exact and identical from run to run.  Non-finite logits: the result is unspecified.
+ * SSBEV_EINVAL, before any pointer is touched: d NULL / non-positive dims / C != 20 / 8 D H W >= 2^31 / B > 65535, logits NULL,
+ * all outputs NULL, conf or n_ignored without label (or without ws), raw without remap.  The workspace (needed for conf /
+ * n_ignored only) is 0 for refused dims and grows with B. */
+size_t ssbev_occ_predict_workspace(const ssbev_upsample_dims* d);
+int ssbev_occ_predict(const float* logits, const uint8_t* label, const uint16_t* remap, uint8_t* pred, uint16_t* raw,
+                      int64_t* conf, int64_t* n_ignored, const ssbev_upsample_dims* d, void* ws, size_t ws_bytes,
+                      ssbev_stream_t stream);
+
 /* Running statistics of a training-mode BatchNorm from the (mean, rstd) ssbev_groupnorm_fwd returned with G == C over the
  * batch: running_mean <- (1-m) running_mean + m mean; running_var <- (1-m) running_var + m var n/(n-1)
  * (torch.nn.BatchNorm3d as built at ViewTransformerLSSVoxel.py:83-88; n = elements per channel). */

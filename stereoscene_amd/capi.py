@@ -260,6 +260,8 @@ SIGNATURES = {
     "ssbev_bri_shell_pre_bwd": (C.c_int, [_P] * 15 + [C.c_int] * 3 + [_P]),
     "ssbev_occ_loss_bwd_workspace": (C.c_size_t, [C.POINTER(UpsampleDims)]),
     "ssbev_occ_loss_bwd": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(UpsampleDims), _P, C.c_size_t, _P]),
+    "ssbev_occ_predict_workspace": (C.c_size_t, [C.POINTER(UpsampleDims)]),
+    "ssbev_occ_predict": (C.c_int, [_P] * 7 + [C.POINTER(UpsampleDims), _P, C.c_size_t, _P]),
     "ssbev_grad_norm_workspace": (C.c_size_t, []),
     "ssbev_grad_norm": (C.c_int, [_P, C.c_int64, _P, _P, C.c_size_t, _P]),
     "ssbev_adamw_step": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.POINTER(AdamWCfg), _P, _P]),

@@ -8,18 +8,18 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .plugin.losses import KITTI_CLASS_NAMES, ssc_counts
+from .plugin.losses import KITTI_CLASS_NAMES, ssc_counts, ssc_counts_from_confusion
 
 CLASS_NAMES = ["unlabeled"] + KITTI_CLASS_NAMES[1:]
 
 
-def evaluate(model, samples, device="cuda", dataset_len=None, sampler=None):
+def evaluate(model, samples, device="cuda", dataset_len=None, sampler=None, fused=False):
     """``eval_results`` dict of the reference (see ``evaluate_counts`` for the arguments)."""
-    return scores_from_counts(evaluate_counts(model, samples, device, dataset_len, sampler).cpu().numpy())
+    return scores_from_counts(evaluate_counts(model, samples, device, dataset_len, sampler, fused=fused).cpu().numpy())
 
 
 @torch.no_grad()
-def evaluate_counts(model, samples, device="cuda", dataset_len=None, sampler=None, reduce=True):
+def evaluate_counts(model, samples, device="cuda", dataset_len=None, sampler=None, reduce=True, fused=False):
     """``samples`` yields dicts with ``img_inputs`` (left10, right10) and ``gt_occ`` [B,X,Y,Z].
     Returns the integer SSC counts (float64 vector: tp, fp, fn, then per-class tp / fp / fn), summed over ranks when a
     process group is initialised and ``reduce``; ``evaluate`` turns them into the reference's ``eval_results`` dict (percent,
@@ -29,7 +29,11 @@ def evaluate_counts(model, samples, device="cuda", dataset_len=None, sampler=Non
     last ranks see duplicates of the first samples.  The reference drops them (``collect_results_cpu`` keeps
     ``ordered_results[:len(dataset)]``, apis/test.py); pass the ``sampler`` (or ``dataset_len`` + the process group's
     rank / world size) and the padded tail is skipped before the counts are accumulated.
-    The module's train / eval mode is restored on exit (the runner has no model handle to do it)."""
+    The module's train / eval mode is restored on exit (the runner has no model handle to do it).
+
+    ``fused=True`` takes ``model.predict`` instead of ``simple_test`` + argmax + ``ssc_counts``: on the GPU the head's epilogue is
+    then one pass over the coarse logits (``functional.occ_predict``) and the counts come from the per-sample confusion
+    matrices it returns -- the same integers, without the up-sampled logits."""
     was_training = model.training
     model.eval()
     rank, world = 0, 1
@@ -48,9 +52,13 @@ def evaluate_counts(model, samples, device="cuda", dataset_len=None, sampler=Non
         seen = 0                      # samples of this rank's block consumed so far
         for s in samples:
             gt = s["gt_occ"].to(device)
-            out = model.simple_test(None, s["img_inputs"], gt_occ=gt)
-            pred = out["output_voxels"].argmax(dim=1)
             nb = gt.shape[0]
+            if fused:
+                out = model.predict(None, s["img_inputs"], gt_occ=gt)
+                conf, nign = out["confusion"], out["n_ignored"]
+            else:
+                out = model.simple_test(None, s["img_inputs"], gt_occ=gt)
+                pred = out["output_voxels"].argmax(dim=1)
             if per_rank is not None:
                 # global position of sample i of this batch in the tiled index list = rank * per_rank + seen + i
                 keep = [i for i in range(nb) if rank * per_rank + seen + i < dataset_len]
@@ -58,8 +66,14 @@ def evaluate_counts(model, samples, device="cuda", dataset_len=None, sampler=Non
                 if not keep:
                     continue
                 if len(keep) < nb:
-                    pred, gt = pred[keep], gt[keep]
-            tp, fp, fn, tpc, fpc, fnc = ssc_counts(pred, gt, len(CLASS_NAMES), recompute_mask=True)
+                    if fused:
+                        conf, nign = conf[keep], nign[keep]
+                    else:
+                        pred, gt = pred[keep], gt[keep]
+            if fused:
+                tp, fp, fn, tpc, fpc, fnc = ssc_counts_from_confusion(conf, nign)
+            else:
+                tp, fp, fn, tpc, fpc, fnc = ssc_counts(pred, gt, len(CLASS_NAMES), recompute_mask=True)
             acc += torch.cat([torch.stack([tp, fp, fn]).double(), tpc.double(), fpc.double(), fnc.double()])
     finally:
         model.train(was_training)
@@ -101,6 +115,50 @@ def save_output_semantic_kitti(output_voxels, save_path, sequence_id, frame_id):
     with open(path, "wb") as f:
         raw.tofile(f)
     return path
+
+
+def save_prediction_semantic_kitti(raw_or_pred, save_path, sequence_id, frame_id):
+    """The file ``save_output_semantic_kitti`` writes, from a label volume instead of logits: ``raw_or_pred`` [X,Y,Z] is either the
+    raw ids (uint16, ``predict(...)["raw_voxels"][i]``: written as they are) or the training ids (uint8,
+    ``predict(...)["pred_voxels"][i]``: ``LEARNING_MAP_INV`` is applied on the host).  Returns the path."""
+    vol = raw_or_pred.cpu().numpy() if isinstance(raw_or_pred, torch.Tensor) else np.asarray(raw_or_pred)
+    if vol.dtype == np.uint16:
+        raw = np.ascontiguousarray(vol).reshape(-1)
+    elif vol.dtype == np.uint8:
+        raw = LEARNING_MAP_INV[vol.reshape(-1)].astype(np.uint16)
+    else:
+        raise TypeError(f"save_prediction_semantic_kitti: uint16 raw ids or uint8 training ids expected, got {vol.dtype}")
+    folder = os.path.join(save_path, "sequences", str(sequence_id), "predictions")
+    os.makedirs(folder, exist_ok=True)
+    path = os.path.join(folder, f"{frame_id}.label")
+    with open(path, "wb") as f:
+        raw.tofile(f)
+    return path
+
+
+@torch.no_grad()
+def write_submission(model, samples, save_path, device="cuda"):
+    """Test-set loop of the reference's save path (apis/test.py:100-139): per sample ``model.predict`` with
+    ``remap=LEARNING_MAP_INV`` and one ``.label`` file per frame, named by ``img_metas`` ``sequence`` / ``frame_id`` (a dict per
+    frame, or a list of them for a batch).  ``samples`` yields dicts with ``img_inputs``, ``img_metas`` and optionally ``gt_occ``
+    (its shape is the label grid; without it the grid is twice the head's).  Returns the list of paths."""
+    was_training = model.training
+    model.eval()
+    paths = []
+    try:
+        for s in samples:
+            metas = s["img_metas"]
+            metas = [metas] if isinstance(metas, dict) else list(metas)
+            gt = s.get("gt_occ")
+            out = model.predict(metas, s["img_inputs"], gt_occ=None if gt is None else gt.to(device), remap=LEARNING_MAP_INV)
+            raw = out["raw_voxels"].cpu()
+            if raw.shape[0] != len(metas):
+                raise ValueError(f"write_submission: {len(metas)} img_metas for a batch of {raw.shape[0]}")
+            for i, m in enumerate(metas):
+                paths.append(save_prediction_semantic_kitti(raw[i], save_path, m["sequence"], m["frame_id"]))
+    finally:
+        model.train(was_training)
+    return paths
 
 
 def load_checkpoint(model, path_or_state, strict=False):

@@ -13,6 +13,7 @@ import ctypes as C
 
 import os
 
+import numpy as np
 import torch
 
 from . import capi, streams
@@ -2220,6 +2221,53 @@ class _OccLossSums(torch.autograd.Function):
 
 def occ_loss_sums(logits, label_u8, class_weight):
     return _OccLossSums.apply(logits, label_u8, class_weight)
+
+
+def occ_predict_supported(logits, size=None):
+    """The fused inference epilogue serves fp32 20-class logits on the GPU and a label grid of exactly twice their size."""
+    return (logits.is_cuda and logits.dim() == 5 and logits.shape[1] == 20 and logits.dtype == torch.float32
+            and (size is None or tuple(int(v) for v in size) == tuple(2 * int(v) for v in logits.shape[2:])))
+
+
+@torch.no_grad()
+def occ_predict(logits, gt_occ=None, remap=None):
+    """Inference epilogue of the head in one pass (``ssbev_occ_predict``): coarse ``logits`` [B,20,d,h,w] ->
+    ``(pred_u8 [B,2d,2h,2w], raw_u16 | None, conf_i64 [B,20,20] | None, n_ignored [B] | None)``.
+    ``pred`` is exactly ``upsample_trilinear(logits, 2x).argmax(1)``; ``raw = remap[pred]`` when a 20-entry ``remap`` (training id ->
+    raw id) is given; with ``gt_occ`` [B,2d,2h,2w] (255 = ignore) the per-sample confusion counts [gt][pred] over the labelled
+    voxels and the number of ignored ones come back too.  The up-sampled logits are never written.  No fallback: CPU tensors, a
+    class count other than 20 or a label grid that is not exactly x2 raise ``SsbevError``."""
+    if not logits.is_cuda:
+        raise capi.SsbevError("occ_predict: ssbev operators run on the MI355X only: got a CPU tensor (no CPU fallback exists)")
+    if logits.dim() != 5 or logits.shape[1] != 20:
+        raise capi.SsbevError(f"occ_predict: logits [B,20,d,h,w] expected, got {tuple(logits.shape)}")
+    lib = capi.load()
+    xcl = to_cl(_f32(logits, "occ_predict"))
+    B, D, H, W, Cch = xcl.shape
+    fine = (B, 2 * D, 2 * H, 2 * W)
+    dev = logits.device
+    d = capi.UpsampleDims(B, D, H, W, Cch)
+    lab = conf = nign = raw = tab = None
+    ws_bytes = 0
+    if gt_occ is not None:
+        if tuple(gt_occ.shape) != fine:
+            raise capi.SsbevError(f"occ_predict: label grid {tuple(gt_occ.shape)} is not exactly twice the logits' {tuple(xcl.shape[:4])}")
+        lab = gt_occ.to(device=dev, dtype=torch.uint8).contiguous()       # classes 0..19, 255 = ignore
+        conf = torch.empty(B, Cch, Cch, dtype=torch.int64, device=dev)
+        nign = torch.empty(B, dtype=torch.int64, device=dev)
+        ws_bytes = lib.ssbev_occ_predict_workspace(C.byref(d))
+    if remap is not None:
+        tab = np.ascontiguousarray(np.asarray(remap).reshape(-1), dtype=np.uint16)
+        if tab.size != Cch:
+            raise capi.SsbevError(f"occ_predict: remap needs {Cch} entries, got {tab.size}")
+        raw = torch.empty(fine, dtype=torch.uint16, device=dev)
+    pred = torch.empty(fine, dtype=torch.uint8, device=dev)
+    ws = _ws(ws_bytes, dev)
+    with _span("occ_predict", 0.0, 4.0 * xcl.numel() + pred.numel() * (1 + (lab is not None) + 2 * (raw is not None)), "fwd   occ_predict"):
+        capi.check(lib.ssbev_occ_predict(capi.ptr(xcl), capi.ptr(lab), None if tab is None else C.c_void_p(tab.ctypes.data),
+                                         capi.ptr(pred), capi.ptr(raw), capi.ptr(conf), capi.ptr(nign), C.byref(d), capi.ptr(ws),
+                                         ws.numel(), capi.stream()), "ssbev_occ_predict")
+    return pred, raw, conf, nign
 
 
 DEPTH_BCE = os.environ.get("SSBEV_DEPTH_BCE", "1") != "0"    # fused depth loss (0 = the ~35 ATen ops of the tensor expression)

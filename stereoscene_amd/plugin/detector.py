@@ -2,6 +2,7 @@
 onwards.  The 2-D image backbone/neck (EfficientNet-B7 + SECONDFPN) is outside the hot path
 (SURVEY 8(f1)): when ``img_backbone`` is absent from the registry the detector expects the
 image-neck feature maps in place of raw images (``img_inputs[k][0]`` = [B,1,640,fH,fW])."""
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as TF
@@ -78,6 +79,41 @@ class BEVDepthOccupancy(nn.Module):
         from ..functional import upsample_trilinear
         out["output_voxels"] = upsample_trilinear(out["output_voxels"][0], gt_occ.shape[1:])
         out["target_voxels"] = gt_occ
+        return out
+
+    @torch.no_grad()
+    def predict(self, img_metas=None, img=None, gt_occ=None, remap=None):
+        """``simple_test`` up to the head, then the label volume instead of the up-sampled logits: ``pred_voxels`` uint8
+        [B,X,Y,Z] (= ``simple_test(...)["output_voxels"].argmax(1)``), ``raw_voxels`` uint16 = ``remap[pred]`` when a 20-entry
+        ``remap`` is given, and with ``gt_occ`` the per-sample ``confusion`` int64 [B,20,20] ([gt][pred]), ``n_ignored`` [B] and
+        their batch total ``ssc_counts`` (tp, fp, fn, tpc, fpc, fnc; SSCMetrics semantics).  On the GPU with a x2 label grid this
+        is one pass of ``functional.occ_predict``; otherwise the upsample -> argmax -> ssc_counts route of ``simple_test`` +
+        ``evaluate``."""
+        from .. import functional as F
+        from .losses import confusion_counts, ssc_counts, ssc_counts_from_confusion
+        voxel_feats, img_feats, depth = self.extract_feat(points=None, img=img, img_metas=img_metas)
+        logits = self.pts_bbox_head(voxel_feats=voxel_feats, points=None, img_metas=img_metas)["output_voxels"][0]
+        size = tuple(gt_occ.shape[1:]) if gt_occ is not None else tuple(2 * int(v) for v in logits.shape[2:])
+        out = {"evaluation_semantic": 0, "target_voxels": gt_occ}
+        if F.occ_predict_supported(logits, size):
+            pred, raw, conf, nign = F.occ_predict(logits, gt_occ, remap)
+            if gt_occ is not None:
+                out["ssc_counts"] = ssc_counts_from_confusion(conf, nign)
+        else:
+            pred = F.upsample_trilinear(logits, size).argmax(dim=1)
+            raw = conf = nign = None
+            if remap is not None:
+                raw = torch.as_tensor(np.asarray(remap).astype(np.int32), device=pred.device)[pred].to(torch.uint16)
+            if gt_occ is not None:
+                gt = gt_occ.to(pred.device)
+                conf, nign = confusion_counts(pred, gt, logits.shape[1])
+                out["ssc_counts"] = ssc_counts(pred, gt, logits.shape[1], recompute_mask=True)
+            pred = pred.to(torch.uint8)
+        out["pred_voxels"] = pred
+        if raw is not None:
+            out["raw_voxels"] = raw
+        if conf is not None:
+            out["confusion"], out["n_ignored"] = conf, nign
         return out
 
     def forward(self, return_loss=True, **kwargs):

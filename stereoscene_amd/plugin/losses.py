@@ -79,6 +79,36 @@ def ssc_counts(pred, gt, n_classes=20, recompute_mask=False):
     return tp, fp, fn, tpc, fpc, fnc
 
 
+def confusion_counts(pred, gt, n_classes=20):
+    """Per-sample confusion of a label volume: (conf int64 [B,n,n] indexed [gt][pred] over the voxels with gt != 255, n_ignored
+    int64 [B]) -- what the fused inference epilogue (``functional.occ_predict``) returns, from tensor ops."""
+    B = gt.shape[0]
+    p, g = pred.reshape(B, -1).long(), gt.reshape(B, -1).long()
+    valid = g != 255
+    key = torch.where(valid, g * n_classes + p, torch.full_like(g, n_classes * n_classes))
+    key = key + torch.arange(B, device=key.device).view(B, 1) * (n_classes * n_classes + 1)
+    cnt = torch.bincount(key.reshape(-1), minlength=B * (n_classes * n_classes + 1)).view(B, -1)
+    return cnt[:, :-1].reshape(B, n_classes, n_classes), cnt[:, -1]
+
+
+def ssc_counts_from_confusion(conf, n_ignored):
+    """``ssc_counts(pred, gt, 20, recompute_mask=True)`` from the confusion counts ``conf`` [20,20] or [B,20,20] ([gt][pred] over
+    the labelled voxels; a batch is summed) and the number of ignored voxels.  SSCMetrics counts an ignored voxel as a
+    (gt 0, pred 0) pair in the per-class statistics (utils/ssc_metric.py:123-169 re-derives the mask from the zeroed target), so
+    ``tpc[0]`` includes them; the completion counts see labelled voxels only.  Integer algebra on 400 numbers, any device."""
+    n = conf.shape[-1]
+    conf = conf.reshape(-1, n, n).sum(0).long()
+    tp = conf[1:, 1:].sum()
+    fp = conf[0, 1:].sum()
+    fn = conf[1:, 0].sum()
+    full = conf.clone()
+    full[0, 0] += torch.as_tensor(n_ignored, device=conf.device).long().sum()
+    tpc = full.diagonal()
+    fpc = full.sum(0) - tpc
+    fnc = full.sum(1) - tpc
+    return tp, fp, fn, tpc, fpc, fnc
+
+
 def _nll1(v):
     return -torch.clamp(torch.log(v), min=-100.0)
 
