@@ -428,6 +428,30 @@ int ssbev_occ_predict(const float* logits, const uint8_t* label, const uint16_t*
                       int64_t* conf, int64_t* n_ignored, const ssbev_upsample_dims* d, void* ws, size_t ws_bytes,
                       ssbev_stream_t stream);
 
+/* Lovasz-softmax voxel loss (since version 104): lovasz_softmax(softmax(up(logits)), label, classes='present', per_image=False,
+ * ignore) of the reference head (lovasz_softmax.py:21-33, 156-225), UNWEIGHTED, on a fused key / segmented-radix-sort / scan
+ * path; the up-sampled logits and the probabilities are never written.
+ *   dims      B, D, H, W: the LOGITS' grid; C == 20; ignore: label value that is skipped (255); upsample 1: the label grid is
+ *             exactly [2D, 2H, 2W] and the logits are up-sampled trilinearly (align_corners=False), 0: labels on [D, H, W]
+ *   logits    [B, D, H, W, 20] channels-last fp32;  label [B, D', H', W'] uint8
+ *   loss      one float (device): mean over the classes present among the labelled voxels; 0 when no voxel is labelled
+ *   dj        [B D' H' W'][20] float (device), kept by the caller for backward: dJ at the rank of voxel v in the descending
+ *             sort of class c's errors; written for labelled voxels and present classes only, never read elsewhere
+ *   counts    [ssbev_lovasz_num_counts()] int32 (device), kept for backward: labelled voxels per class [20], M, n_present
+ *   backward  grad_logits [B, D, H, W, 20] = grad_out[0] * d loss / d logits (grad_out: one float on the device)
+ * Nothing is read back to the host.  Ties in the errors keep voxel order (stable LSD sort, ballot ranking): every run gives
+ * the same bits.  SSBEV_EINVAL before any device work: NULL pointers, non-positive dims, C != 20, upsample not 0 / 1,
+ * 20 x voxels >= 2^31;  SSBEV_EWORKSPACE: ws_bytes below the query.  The queries answer 0 for refused dims. */
+typedef struct { int B, D, H, W, C, ignore, upsample; } ssbev_lovasz_dims;
+int ssbev_lovasz_num_counts(void);
+size_t ssbev_lovasz_workspace(const ssbev_lovasz_dims* d);
+int ssbev_lovasz_fwd(const float* logits, const uint8_t* label, float* loss, float* dj, int32_t* counts,
+                     const ssbev_lovasz_dims* d, void* ws, size_t ws_bytes, ssbev_stream_t stream);
+size_t ssbev_lovasz_bwd_workspace(const ssbev_lovasz_dims* d);
+int ssbev_lovasz_bwd(const float* logits, const uint8_t* label, const float* dj, const int32_t* counts,
+                     const float* grad_out, float* grad_logits, const ssbev_lovasz_dims* d, void* ws, size_t ws_bytes,
+                     ssbev_stream_t stream);
+
 /* Running statistics of a training-mode BatchNorm from the (mean, rstd) ssbev_groupnorm_fwd returned with G == C over the
  * batch: running_mean <- (1-m) running_mean + m mean; running_var <- (1-m) running_var + m var n/(n-1)
  * (torch.nn.BatchNorm3d as built at ViewTransformerLSSVoxel.py:83-88; n = elements per channel). */

@@ -86,6 +86,10 @@ class UpsampleDims(C.Structure):
     _fields_ = [("B", C.c_int), ("D", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int)]
 
 
+class LovaszDims(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("B", "D", "H", "W", "C", "ignore", "upsample")]
+
+
 class GemmDims(C.Structure):
     _fields_ = [("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("batch", C.c_int),
                 ("lda", C.c_int64), ("ldb", C.c_int64), ("ldc", C.c_int64), ("sa", C.c_int64), ("sb", C.c_int64), ("sc", C.c_int64),
@@ -262,6 +266,11 @@ SIGNATURES = {
     "ssbev_occ_loss_bwd": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(UpsampleDims), _P, C.c_size_t, _P]),
     "ssbev_occ_predict_workspace": (C.c_size_t, [C.POINTER(UpsampleDims)]),
     "ssbev_occ_predict": (C.c_int, [_P] * 7 + [C.POINTER(UpsampleDims), _P, C.c_size_t, _P]),
+    "ssbev_lovasz_num_counts": (C.c_int, []),
+    "ssbev_lovasz_workspace": (C.c_size_t, [C.POINTER(LovaszDims)]),
+    "ssbev_lovasz_fwd": (C.c_int, [_P] * 5 + [C.POINTER(LovaszDims), _P, C.c_size_t, _P]),
+    "ssbev_lovasz_bwd_workspace": (C.c_size_t, [C.POINTER(LovaszDims)]),
+    "ssbev_lovasz_bwd": (C.c_int, [_P] * 6 + [C.POINTER(LovaszDims), _P, C.c_size_t, _P]),
     "ssbev_grad_norm_workspace": (C.c_size_t, []),
     "ssbev_grad_norm": (C.c_int, [_P, C.c_int64, _P, _P, C.c_size_t, _P]),
     "ssbev_adamw_step": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.POINTER(AdamWCfg), _P, _P]),

@@ -29,7 +29,7 @@ const char* ssbev_env(const char* name) {
 }
 
 extern "C" {
-int ssbev_version(void) { return 103; /* 0.1.3: + ssbev_occ_predict */ }
+int ssbev_version(void) { return 104; /* 0.1.4: + ssbev_lovasz_* */ }
 const char* ssbev_build_arch(void) { return "gfx950"; }
 
 // Forget every switch read so far: the next use of a name reads the environment again.  (Switches that a launch helper folded

@@ -2270,6 +2270,72 @@ def occ_predict(logits, gt_occ=None, remap=None):
     return pred, raw, conf, nign
 
 
+LOVASZ = os.environ.get("SSBEV_LOVASZ", "1") != "0"          # fused Lovasz-softmax (0 = the tensor form: softmax + one torch.sort per class)
+
+
+def lovasz_supported(logits, label):
+    """The fused Lovasz-softmax serves fp32 20-class logits on the GPU that sit on the label grid or at exactly half of it."""
+    if not (logits.is_cuda and logits.dim() == 5 and logits.shape[1] == 20 and logits.dtype == torch.float32 and label.dim() == 4
+            and label.shape[0] == logits.shape[0]):
+        return False
+    fine, coarse = tuple(int(v) for v in label.shape[1:]), tuple(int(v) for v in logits.shape[2:])
+    return fine == coarse or fine == tuple(2 * v for v in coarse)
+
+
+class _LovaszSoftmax(torch.autograd.Function):
+    """logits [B,20,D,H,W], label uint8 [B,D',H',W'] (the same grid or exactly twice it) -> the unweighted Lovasz-softmax loss
+    (0-dim fp32), ``ssbev_lovasz_fwd / _bwd``.  Forward keeps dJ per [voxel][class] and the per-class counts on the device;
+    nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, logits, label_u8, ignore):
+        lib = capi.load()
+        xcl = to_cl(_f32(logits, "lovasz_softmax"))
+        B, D, H, W, Cch = xcl.shape
+        lab = label_u8.contiguous()
+        up = int(tuple(lab.shape[1:]) != (D, H, W))
+        d = capi.LovaszDims(B, D, H, W, Cch, int(ignore), up)
+        dev = logits.device
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        dj = torch.empty(lab.numel(), Cch, dtype=torch.float32, device=dev)
+        counts = torch.empty(lib.ssbev_lovasz_num_counts(), dtype=torch.int32, device=dev)
+        ws = _ws(lib.ssbev_lovasz_workspace(C.byref(d)), dev)
+        with _span("lovasz", 0.0, 4.0 * xcl.numel() + lab.numel() + 4.0 * 37 * dj.numel(), "fwd   lovasz"):
+            capi.check(lib.ssbev_lovasz_fwd(capi.ptr(xcl), capi.ptr(lab), capi.ptr(loss), capi.ptr(dj), capi.ptr(counts),
+                                            C.byref(d), capi.ptr(ws), ws.numel(), capi.stream()), "ssbev_lovasz_fwd")
+        ctx.save_for_backward(xcl, lab, dj, counts)
+        ctx.dims = d
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = capi.load()
+        xcl, lab, dj, counts = ctx.saved_tensors
+        d = ctx.dims
+        gl = g.to(torch.float32).reshape(1).contiguous()
+        gx = torch.empty_like(xcl)
+        ws = _ws(lib.ssbev_lovasz_bwd_workspace(C.byref(d)), xcl.device)
+        with _span("lovasz", 0.0, 8.0 * xcl.numel() + lab.numel() + 8.0 * dj.numel(), "bwd   lovasz"):
+            capi.check(lib.ssbev_lovasz_bwd(capi.ptr(xcl), capi.ptr(lab), capi.ptr(dj), capi.ptr(counts), capi.ptr(gl),
+                                            capi.ptr(gx), C.byref(d), capi.ptr(ws), ws.numel(), capi.stream()),
+                       "ssbev_lovasz_bwd")
+        return from_cl(gx), None, None
+
+
+def lovasz_softmax(logits, label_u8, ignore=255):
+    """Unweighted Lovasz-softmax loss of ``softmax(up(logits))`` against ``label_u8`` over the labelled voxels of the whole batch
+    (classes present in the labels only; 0 with a zero gradient when no voxel is labelled), fp32, 0-dim.  Supported inputs
+    (``lovasz_supported``) with ``LOVASZ`` on run on the fused HIP path; anything else on the tensor form of plugin/losses.py
+    after ``upsample_trilinear``."""
+    label_u8 = label_u8.to(torch.uint8)
+    if LOVASZ and lovasz_supported(logits, label_u8):
+        return _LovaszSoftmax.apply(logits, label_u8, int(ignore))
+    from .plugin import losses
+    if not LOVASZ and logits.is_cuda:
+        return losses.lovasz_softmax_tensor(upsample_trilinear(logits, label_u8.shape[-3:]), label_u8, ignore).float()
+    return losses.lovasz_softmax_loss(logits, label_u8, ignore).float()
+
+
 DEPTH_BCE = os.environ.get("SSBEV_DEPTH_BCE", "1") != "0"    # fused depth loss (0 = the ~35 ATen ops of the tensor expression)
 
 

@@ -113,7 +113,47 @@ def _nll1(v):
     return -torch.clamp(torch.log(v), min=-100.0)
 
 
-def occ_losses_fused(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0, w_geo=1.0, compute_metric=False):
+def lovasz_softmax_tensor(logits, target, ignore=255):
+    """Lovasz-softmax (lovasz_softmax.py:21-33, 156-225 with classes='present', per_image=False) of logits that already sit on
+    the label grid, from tensor ops on any device and in the logits' dtype: ignored voxels dropped, one descending sort per class
+    present in the labels, mean over those classes; a zero with a zero gradient when no voxel is labelled."""
+    n_cls = logits.shape[1]
+    valid = target != ignore
+    p = torch.softmax(logits, dim=1).permute(0, 2, 3, 4, 1)[valid]   # [M, C]
+    t = target[valid].long()                                          # [M]
+    if t.numel() == 0:
+        return logits.sum() * 0.0
+    cnt = torch.bincount(t, minlength=n_cls)[:n_cls]
+    losses = []
+    for c in torch.nonzero(cnt).flatten().tolist():
+        fg = (t == c).to(p.dtype)
+        err, perm = torch.sort((fg - p[:, c]).abs(), 0, descending=True)
+        fg_sorted = fg[perm]
+        total = fg_sorted.sum()
+        jac = 1.0 - (total - fg_sorted.cumsum(0)) / (total + (1.0 - fg_sorted).cumsum(0))
+        losses.append(torch.dot(err, torch.cat((jac[:1], jac[1:] - jac[:-1]))))
+    if not losses:                                                    # labelled voxels, but none of a known class
+        return logits.sum() * 0.0
+    return torch.stack(losses).mean()
+
+
+def lovasz_softmax_loss(logits, gt_occ, ignore=255):
+    """Unweighted Lovasz-softmax voxel loss of the head (occhead.py:284-287, 321-324): logits [B,C,d,h,w] are up-sampled
+    trilinearly to the grid of ``gt_occ`` [B,D,H,W].  The fused HIP path serves what ``functional.lovasz_supported`` accepts;
+    everything else (other devices, dtypes, class counts or ratios, ``SSBEV_LOVASZ=0``) runs ``lovasz_softmax_tensor``."""
+    from .. import functional as F
+    if F.LOVASZ and F.lovasz_supported(logits, gt_occ):
+        return F.lovasz_softmax(logits, gt_occ, ignore)
+    if logits.shape[-3:] != gt_occ.shape[-3:]:
+        if logits.is_cuda:
+            logits = F.upsample_trilinear(logits, gt_occ.shape[-3:])
+        else:                                                         # (the HIP up-sampling has no CPU form)
+            logits = TF.interpolate(logits, size=tuple(gt_occ.shape[-3:]), mode="trilinear", align_corners=False)
+    return lovasz_softmax_tensor(logits, gt_occ, ignore)
+
+
+def occ_losses_fused(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0, w_geo=1.0, compute_metric=False,
+                     w_lovasz=0.0):
     """Same losses / metric as ``occ_losses`` from the sums of the fused HIP epilogue (one pass over the coarse
     logits; the up-sampled logits, probabilities and one-hot volumes are never materialised)."""
     from .. import functional as F
@@ -130,6 +170,8 @@ def occ_losses_fused(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0
             out[f"loss_voxel_sem_scal_{tag}"] = sem
         if w_geo > 0:
             out[f"loss_voxel_geo_scal_{tag}"] = geo
+        if w_lovasz > 0:
+            out[f"loss_voxel_lovasz_{tag}"] = lovasz_softmax_loss(logits, gt_occ) * w_lovasz
         if compute_metric:
             out[f"sc_iou_{tag}"], out[f"ssc_miou_{tag}"] = iou.detach(), miou.detach()
         return out
@@ -152,6 +194,8 @@ def occ_losses_fused(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0
         inter = occ_t - (sum_p[0] - nom[0])
         geo = _nll1(inter / (M - sum_p[0])) + _nll1(inter / occ_t) + _nll1(nom[0] / cnt[0])
         out[f"loss_voxel_geo_scal_{tag}"] = geo.float() * w_geo
+    if w_lovasz > 0:
+        out[f"loss_voxel_lovasz_{tag}"] = lovasz_softmax_loss(logits, gt_occ) * w_lovasz
     if compute_metric:
         with torch.no_grad():
             tp = conf[1:, 1:].sum()
@@ -165,10 +209,10 @@ def occ_losses_fused(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0
     return out
 
 
-def occ_losses(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0, w_geo=1.0, compute_metric=False):
-    """occhead.py:291-361: trilinear upsample to the label grid, CE + sem_scal + geo_scal (+ metric)."""
+def occ_losses(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0, w_geo=1.0, compute_metric=False, w_lovasz=0.0):
+    """occhead.py:291-361: trilinear upsample to the label grid, CE + sem_scal + geo_scal (+ Lovasz-softmax, + metric)."""
     if (logits.is_cuda and logits.shape[1] == 20 and all(o == 2 * i for o, i in zip(gt_occ.shape[-3:], logits.shape[-3:]))):
-        return occ_losses_fused(logits, gt_occ, class_weights, tag, w_ce, w_sem, w_geo, compute_metric)
+        return occ_losses_fused(logits, gt_occ, class_weights, tag, w_ce, w_sem, w_geo, compute_metric, w_lovasz)
     if logits.shape[-3:] != gt_occ.shape[-3:]:
         from ..functional import upsample_trilinear
         logits = upsample_trilinear(logits, gt_occ.shape[-3:])
@@ -182,6 +226,8 @@ def occ_losses(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0, w_ge
             out[f"loss_voxel_sem_scal_{tag}"] = sem * w_sem
         if w_geo > 0:
             out[f"loss_voxel_geo_scal_{tag}"] = geo * w_geo
+    if w_lovasz > 0:
+        out[f"loss_voxel_lovasz_{tag}"] = lovasz_softmax_loss(logits, gt_occ) * w_lovasz
     if compute_metric:
         with torch.no_grad():
             tp, fp, fn, tpc, fpc, fnc = ssc_counts(logits.argmax(1), t)

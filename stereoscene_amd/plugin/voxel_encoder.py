@@ -147,7 +147,7 @@ class OccHead(nn.Module):
         # a stream synchronisation right before the losses) without adding a state-dict key the reference does not have
         self.register_buffer("class_weights", L.semkitti_class_weights(), persistent=False)
         self.semkitti_loss_weight_cfg = semkitti_loss_weight_cfg or {}
-        for k in ("voxel_ohem", "voxel_lovasz", "frustum_dist", "voxel_dice", "voxel_lga"):
+        for k in ("voxel_ohem", "frustum_dist", "voxel_dice", "voxel_lga"):
             if self.semkitti_loss_weight_cfg.get(k, 0.0) > 0:
                 raise NotImplementedError(f"loss '{k}' is disabled in the reference config and not built")
 
@@ -162,7 +162,7 @@ class OccHead(nn.Module):
         w = self.semkitti_loss_weight_cfg
         return L.occ_losses(output_voxels, target_voxels, self.class_weights.to(output_voxels), tag,
                             w.get("voxel_ce", 0.0), w.get("voxel_sem_scal", 0.0), w.get("voxel_geo_scal", 0.0),
-                            compute_metric)
+                            compute_metric, w.get("voxel_lovasz", 0.0))
 
     def loss(self, output_voxels=None, target_voxels=None, output_points=None, target_points=None, img_metas=None,
              **kwargs):

@@ -33,6 +33,45 @@ def hash_normal(name, shape, std=1.0):
     return (acc * (std * math.sqrt(3.0))).float()
 
 
+# Cases of the Lovasz-softmax tests (tools/make_golden_lovasz.py records the reference on them): name -> (logits shape, label
+# grid).  A / B are up-sampled x2, C is A at the label resolution, D all-zero logits (two big tie groups per class), E nothing
+# labelled, F two labelled voxels of two classes, G fewer voxels than one wave.
+LOVASZ_CASES = {"A": ((2, 20, 8, 6, 4), (2, 16, 12, 8)), "B": ((1, 20, 16, 16, 8), (1, 32, 32, 16)),
+                "C": ((2, 20, 16, 12, 8), (2, 16, 12, 8)), "D": ((2, 20, 8, 6, 4), (2, 16, 12, 8)),
+                "E": ((2, 20, 8, 6, 4), (2, 16, 12, 8)), "F": ((2, 20, 8, 6, 4), (2, 16, 12, 8)),
+                "G": ((1, 20, 3, 2, 2), (1, 6, 4, 4))}
+LOVASZ_SEED = {"A": 0, "B": 0, "C": 0, "G": 0}      # bumped when a fixture's fp32-vs-float64 gradient spread is above 2.5e-5
+
+
+def lovasz_labels(tag, shape):
+    """uint8 labels: ~10 % ignored (255), a skewed distribution over the classes (0 dominant), 2, 3 and 8 absent."""
+    classes = torch.tensor([c for c in range(20) if c not in (2, 3, 8)], dtype=torch.uint8)
+    u = hash_uniform(f"{tag}_cls", shape, 0.0, 1.0).double()
+    lab = classes[(u ** 2.5 * len(classes)).long().clamp_(max=len(classes) - 1)]
+    lab[hash_uniform(f"{tag}_ign", shape, 0.0, 1.0) < 0.1] = 255
+    return lab
+
+
+def lovasz_case(name):
+    """(logits fp32 [B,20,d,h,w] ~ N(0, 2^2), labels uint8 [B,D,H,W]) of LOVASZ_CASES[name]."""
+    coarse, fine = LOVASZ_CASES[name]
+    base = "A" if name in "CDEF" else name
+    lab = lovasz_labels(f"lovasz_{base}{LOVASZ_SEED[base]}", fine)
+    if base == "A":
+        lab[0][lab[0] == 19] = 0                       # class 19 occurs in sample 1 only: the batch is ONE set of voxels
+    src = name if name in LOVASZ_SEED else "A"
+    logits = hash_normal(f"lovasz_{src}{LOVASZ_SEED[src]}_x", coarse, 2.0)
+    if name == "D":
+        logits = torch.zeros(coarse)
+    if name == "E":
+        lab = torch.full(fine, 255, dtype=torch.uint8)
+    if name == "F":
+        lab = torch.full(fine, 255, dtype=torch.uint8)
+        lab.view(-1)[5] = 4
+        lab.view(-1)[1999] = 9
+    return logits, lab
+
+
 _NORM_TOKENS = (".bn", ".gn", "norm")
 
 
