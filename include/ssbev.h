@@ -204,6 +204,13 @@ size_t ssbev_conv_packed_weight_elems(const ssbev_conv_dims* d);
  * strided / transposed / dilated layers whose gather source has a multiple of 32 channels and whose destination has >= 64;
  * SSBEV_IGEMM=0 or tile_hint >= 10 keep class 0); bf16 storage: 21 = conv_igemm16_kernel (SSBEV_IGEMM16=0 keeps 16). */
 int ssbev_conv_kernel_class(const ssbev_conv_dims* d, int mode);
+/* Host-side plan query (since ssbev_version() 105; no device work): the row-walking kernels give every workgroup a CHUNK of
+ * consecutive row groups of one w-segment and walk them through an LDS ring.  Modes 0 / 1: the chunk length (row groups per
+ * workgroup) the launch of this problem will use when ssbev_conv_kernel_class reports class 1, 2, 3, 7, 8, 9 or 17; a row
+ * group is one row (classes 1, 3, 17), a row pair (2; 7: of the destination, 8: of the coarse grid) or a 2 x 2 (plane, row)
+ * block (9).  Mode 2: the chunk length of wgrad_tapdh_kernel (2 x 2 blocks) when ssbev_conv_bwd_weight takes that kernel.
+ * 0 in every other case.  The launchers call the same plan functions, so the answer is the launch's own. */
+int ssbev_conv_chunk_groups(const ssbev_conv_dims* d, int mode);
 
 /* 32 -> 1 / 2 / 4 channel 3x3x3 stride-1 "same" layers (the 32 -> 1 classifiers of the cost-volume stack,
  * ViewTransformerLSSVoxel.py:185-187, 239-241; mode 1: the data gradient of a 1 / 2 / 4 -> 32 layer) as one pass over the

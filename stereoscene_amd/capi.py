@@ -135,6 +135,7 @@ SIGNATURES = {
     "ssbev_gwc_warp_bwd_fused": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(GwcDims), _P, C.c_size_t, _P]),
     "ssbev_conv_packed_weight_elems": (C.c_size_t, [C.POINTER(ConvDims)]),
     "ssbev_conv_kernel_class": (C.c_int, [C.POINTER(ConvDims), C.c_int]),
+    "ssbev_conv_chunk_groups": (C.c_int, [C.POINTER(ConvDims), C.c_int]),
     "ssbev_frustum_geometry": (C.c_int, [_P] * 9 + [C.POINTER(GeomDims), _P]),
     "ssbev_conv_pack_weight": (C.c_int, [_P, _P, C.POINTER(ConvDims), C.c_int, _P]),
     "ssbev_conv_thin_workspace": (C.c_size_t, [C.POINTER(ConvDims), C.c_int]),

@@ -1337,8 +1337,9 @@ int dispatch_gather16(const bf16_t* x, const bf16_t* wp, const float* bias, YT* 
   }
 }
 
-template <typename YT>
-int launch_tap16(const bf16_t* x, const float* wp, const float* bias, YT* y, const ssbev_conv_dims* d, int mode, hipStream_t st) {
+// the geometry launch_tap16 hands to conv_tap16_kernel, g.gpc (rows per workgroup chunk) included; shared with the host-side
+// plan query (ssbev_bf16::tap_chunk_groups).  has_bias is the launcher's to fill in
+Tap16Geom plan_tap16(const ssbev_conv_dims* d, int mode) {
   Tap16Geom g;
   g.B = d->B; g.D = d->Do; g.H = d->Ho; g.W = d->Wo;
   g.K = mode == 0 ? d->Cin : d->Cout;
@@ -1346,7 +1347,7 @@ int launch_tap16(const bf16_t* x, const float* wp, const float* bias, YT* y, con
   g.nseg = (g.W + kT16Wseg - 1) / kT16Wseg;
   g.NG = g.B * g.D * g.H;
   g.relu = mode == 0 ? d->relu : 0;
-  g.has_bias = (mode == 0 && bias) ? 1 : 0;
+  g.has_bias = 0;
   g.accumulate = d->accumulate;
   // three workgroups per CU (42.5 KB of LDS each): whole rounds of 768 workgroups, >= 24 rows each
   long nranges = 768 / g.nseg;
@@ -1357,7 +1358,14 @@ int launch_tap16(const bf16_t* x, const float* wp, const float* bias, YT* y, con
   if (const char* e = ssbev_tune("SSBEV_TAP16_RANGES")) { const long v = atol(e); if (v > 0) nranges = v; }   // tuning hook
   if (nranges < 1) nranges = 1;
   g.gpc = (int)((g.NG + nranges - 1) / nranges);
-  nranges = (g.NG + g.gpc - 1) / g.gpc;
+  return g;
+}
+
+template <typename YT>
+int launch_tap16(const bf16_t* x, const float* wp, const float* bias, YT* y, const ssbev_conv_dims* d, int mode, hipStream_t st) {
+  Tap16Geom g = plan_tap16(d, mode);
+  g.has_bias = (mode == 0 && bias) ? 1 : 0;
+  const long nranges = (g.NG + g.gpc - 1) / g.gpc;
   auto kern = conv_tap16_kernel<YT>;
   hipLaunchKernelGGL(kern, dim3((unsigned)(nranges * g.nseg)), dim3(256), kT16LdsBytes, st, x, reinterpret_cast<const uint4*>(wp),
                      bias, y, g);
@@ -1480,6 +1488,10 @@ int kernel_class(const ssbev_conv_dims* d, int mode) {
   if (wide16_ntl(d, mode)) return 19;
   if (tap16_applicable(d, mode)) return 17;
   return conv_igemm16_applicable(make_geom(d, mode), d->tile_hint >= 10 ? d->tile_hint : 0) ? 21 : 16;
+}
+
+int tap_chunk_groups(const ssbev_conv_dims* d, int mode) {
+  return dims_ok(d, mode) && kernel_class(d, mode) == 17 ? plan_tap16(d, mode).gpc : 0;
 }
 
 size_t packed_elems(const ssbev_conv_dims* d) {

@@ -3861,8 +3861,10 @@ bool conv_thin_applicable(const ssbev_conv_dims* d, int mode) {
   return d->tile_hint == 9 || (long)d->B * d->Do * d->Ho * ((d->Wo + kTapWseg - 1) / kTapWseg) >= 1024L * 16;
 }
 
-int launch_conv_thin(const float* x, const float* wt, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
-                     hipStream_t st) {
+// Chunk plans of the row-walking kernels: the geometry a launcher hands to its kernel, g.gpc (row groups per workgroup chunk)
+// included.  Each launcher below and ssbev_conv_chunk_groups (the host-side plan query) call the SAME plan_* function, so the
+// query cannot drift from the launch.  has_bias is the launcher's to fill in (it depends on a pointer, not on the dims).
+ConvTapGeom plan_conv_thin(const ssbev_conv_dims* d, int mode) {
   ConvTapGeom g;
   g.B = d->B; g.D = d->Do; g.H = d->Ho; g.W = d->Wo;
   g.K = mode == 0 ? d->Cin : d->Cout;
@@ -3870,11 +3872,18 @@ int launch_conv_thin(const float* x, const float* wt, const float* bias, float* 
   g.nseg = (g.W + kTapWseg - 1) / kTapWseg;
   g.NG = g.B * g.D * g.H;
   g.relu = mode == 0 ? d->relu : 0;
-  g.has_bias = (mode == 0 && bias) ? 1 : 0;
+  g.has_bias = 0;
   long nranges = std::max(1L, 1024L / g.nseg);
   if (nranges > g.NG) nranges = g.NG;
   g.gpc = (int)((g.NG + nranges - 1) / nranges);
-  nranges = (g.NG + g.gpc - 1) / g.gpc;
+  return g;
+}
+
+int launch_conv_thin(const float* x, const float* wt, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
+                     hipStream_t st) {
+  ConvTapGeom g = plan_conv_thin(d, mode);
+  g.has_bias = (mode == 0 && bias) ? 1 : 0;
+  const long nranges = (g.NG + g.gpc - 1) / g.gpc;
   const size_t lds = (size_t)(kTapRingF + 27 * kThinNP * 32) * sizeof(float);
   auto kern = conv_thin_kernel;
   if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -3905,8 +3914,23 @@ bool conv_tap2_applicable(const ssbev_conv_dims* d, int mode) {
   return d->tile_hint == 5 || (long)d->B * Dd * ((Hd + 1) / 2) * ((Wd + 15) / 16) >= 256L * 8;
 }
 
-int launch_conv_tap2(const float* x, const float* wp, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
-                     hipStream_t st) {
+// Chunk length of the one-workgroup-per-CU walks (NG row groups in all, H2 of them per plane or plane pair), by a small cost
+// model: whole rounds of 256 workgroups matter most (the last round's idle CUs), then the start-up of a chunk (`startup` row
+// groups) and the ring restage at every plane crossing inside a chunk (`crossing` row groups each).  The first minimum wins.
+int chunk_groups_by_rounds(int NG, int nseg, int H2, int cmax, double startup, double crossing) {
+  double best = 1e30;
+  int gpc = 1;
+  for (int c = 1; c <= NG && c <= cmax; ++c) {
+    const long blocks = (long)((NG + c - 1) / c) * nseg;
+    const long rounds = (blocks + 255) / 256;
+    const double crossings = H2 % c == 0 ? 0.0 : (c % H2 == 0 ? c / H2 - 1 : (double)c / H2);
+    const double cost = rounds * (c + startup + crossing * crossings);
+    if (cost < best) { best = cost; gpc = c; }
+  }
+  return gpc;
+}
+
+ConvTapGeom plan_conv_tap2(const ssbev_conv_dims* d, int mode) {
   ConvTapGeom g;
   g.B = d->B;
   g.Ds = mode == 0 ? d->Di : d->Do; g.Hs = mode == 0 ? d->Hi : d->Ho; g.Ws = mode == 0 ? d->Wi : d->Wo;
@@ -3917,19 +3941,18 @@ int launch_conv_tap2(const float* x, const float* wp, const float* bias, float* 
   const int H2 = (g.H + 1) / 2;
   g.NG = g.B * g.D * H2;                     // output row pairs
   g.relu = mode == 0 ? d->relu : 0;
-  g.has_bias = (mode == 0 && bias) ? 1 : 0;
+  g.has_bias = 0;
   g.accumulate = d->accumulate;
   // one 512-thread workgroup per CU (150 KB of LDS): whole rounds of 256 workgroups, chunk start-up ~1 pair, plane crossing ~0.5
-  double best = 1e30;
-  g.gpc = 1;
-  for (int c = 1; c <= g.NG && c <= 96; ++c) {
-    const long blocks = (long)((g.NG + c - 1) / c) * g.nseg;
-    const long rounds = (blocks + 255) / 256;
-    const double crossings = H2 % c == 0 ? 0.0 : (c % H2 == 0 ? c / H2 - 1 : (double)c / H2);
-    const double cost = rounds * (c + 1.0 + 0.5 * crossings);
-    if (cost < best) { best = cost; g.gpc = c; }
-  }
+  g.gpc = chunk_groups_by_rounds(g.NG, g.nseg, H2, 96, 1.0, 0.5);
   if (const char* e = ssbev_tune("SSBEV_TAP2_GPC")) { const int v = atoi(e); if (v > 0) g.gpc = v; }   // tuning hook
+  return g;
+}
+
+int launch_conv_tap2(const float* x, const float* wp, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
+                     hipStream_t st) {
+  ConvTapGeom g = plan_conv_tap2(d, mode);
+  g.has_bias = (mode == 0 && bias) ? 1 : 0;
   const long nranges = (g.NG + g.gpc - 1) / g.gpc;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tap2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)kT2LdsBytes) != hipSuccess)
@@ -3957,8 +3980,7 @@ bool conv_tap2up_applicable(const ssbev_conv_dims* d, int mode) {
   return d->tile_hint == 5 || (long)d->B * Ds * ((Hs + 1) / 2) * ((Ws + 15) / 16) >= 256L * 8;
 }
 
-int launch_conv_tap2up(const float* x, const float* wp, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
-                       hipStream_t st) {
+ConvTapGeom plan_conv_tap2up(const ssbev_conv_dims* d, int mode) {
   ConvTapGeom g;
   g.B = d->B;
   g.Ds = mode == 0 ? d->Di : d->Do; g.Hs = mode == 0 ? d->Hi : d->Ho; g.Ws = mode == 0 ? d->Wi : d->Wo;
@@ -3969,18 +3991,17 @@ int launch_conv_tap2up(const float* x, const float* wp, const float* bias, float
   const int H2 = (g.Hs + 1) / 2;
   g.NG = g.B * g.Ds * H2;                    // coarse row pairs
   g.relu = mode == 0 ? d->relu : 0;
-  g.has_bias = (mode == 0 && bias) ? 1 : 0;
+  g.has_bias = 0;
   g.accumulate = d->accumulate;
-  double best = 1e30;
-  g.gpc = 1;
-  for (int c = 1; c <= g.NG && c <= 96; ++c) {
-    const long blocks = (long)((g.NG + c - 1) / c) * g.nseg;
-    const long rounds = (blocks + 255) / 256;
-    const double crossings = H2 % c == 0 ? 0.0 : (c % H2 == 0 ? c / H2 - 1 : (double)c / H2);
-    const double cost = rounds * (c + 1.0 + 0.5 * crossings);
-    if (cost < best) { best = cost; g.gpc = c; }
-  }
+  g.gpc = chunk_groups_by_rounds(g.NG, g.nseg, H2, 96, 1.0, 0.5);          // as plan_conv_tap2
   if (const char* e = ssbev_tune("SSBEV_TAP2UP_GPC")) { const int v = atoi(e); if (v > 0) g.gpc = v; }   // tuning hook
+  return g;
+}
+
+int launch_conv_tap2up(const float* x, const float* wp, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
+                       hipStream_t st) {
+  ConvTapGeom g = plan_conv_tap2up(d, mode);
+  g.has_bias = (mode == 0 && bias) ? 1 : 0;
   const long nranges = (g.NG + g.gpc - 1) / g.gpc;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tap2up_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)kUpLdsBytes) != hipSuccess)
@@ -4046,8 +4067,7 @@ bool conv_tapdh_applicable(const ssbev_conv_dims* d, int mode) {
   return !off && conv_taph_applicable(d, mode) && d->Do % 2 == 0 && d->tile_hint != 4;
 }
 
-int launch_conv_tapdh(const float* x, const float* wp, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
-                      hipStream_t st) {
+ConvTapGeom plan_conv_tapdh(const ssbev_conv_dims* d, int mode) {
   ConvTapGeom g;
   g.B = d->B; g.D = d->Do; g.H = d->Ho; g.W = d->Wo;
   g.K = mode == 0 ? d->Cin : d->Cout;
@@ -4055,21 +4075,19 @@ int launch_conv_tapdh(const float* x, const float* wp, const float* bias, float*
   g.nseg = (g.W + kTapWseg - 1) / kTapWseg;
   g.NG = g.B * (g.D / 2) * (g.H / 2);        // 2 x 2 (plane, row) blocks
   g.relu = mode == 0 ? d->relu : 0;
-  g.has_bias = (mode == 0 && bias) ? 1 : 0;
+  g.has_bias = 0;
   g.accumulate = d->accumulate;
-  // one 1024-thread workgroup per CU (149 KB of LDS); chunk length as in launch_conv_taph: whole rounds of 256 workgroups,
+  // one 1024-thread workgroup per CU (149 KB of LDS); chunk length as in plan_conv_taph: whole rounds of 256 workgroups,
   // then the start-up of a chunk (weights + first four rows of four planes) and the restage at every plane-pair crossing
-  const int H2 = g.H / 2;
-  double best = 1e30;
-  g.gpc = 1;
-  for (int c = 1; c <= g.NG && c <= 96; ++c) {
-    const long blocks = (long)((g.NG + c - 1) / c) * g.nseg;
-    const long rounds = (blocks + 255) / 256;
-    const double crossings = H2 % c == 0 ? 0.0 : (c % H2 == 0 ? c / H2 - 1 : (double)c / H2);
-    const double cost = rounds * (c + 0.5 + 0.3 * crossings);
-    if (cost < best) { best = cost; g.gpc = c; }
-  }
+  g.gpc = chunk_groups_by_rounds(g.NG, g.nseg, g.H / 2, 96, 0.5, 0.3);
   if (const char* e = ssbev_tune("SSBEV_TAPDH_GPC")) { const int v = atoi(e); if (v > 0) g.gpc = v; }   // tuning hook
+  return g;
+}
+
+int launch_conv_tapdh(const float* x, const float* wp, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
+                      hipStream_t st) {
+  ConvTapGeom g = plan_conv_tapdh(d, mode);
+  g.has_bias = (mode == 0 && bias) ? 1 : 0;
   const long nranges = (g.NG + g.gpc - 1) / g.gpc;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tapdh_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)kDhLdsBytes) != hipSuccess)
@@ -4132,17 +4150,8 @@ WgradDhPlan plan_wgrad_dh(const ssbev_conv_dims* d) {
   g.nseg = nseg;
   g.NG = g.B * (g.D / 2) * (g.H / 2);
   // one 1024-thread workgroup per CU; the chunk partials (48 tiles per chunk) are folded afterwards, so ONE round of long
-  // chunks: whole rounds of 256 workgroups, start-up + plane-pair crossings as in launch_conv_tapdh
-  const int H2 = g.H / 2;
-  double best = 1e30;
-  g.gpc = 1;
-  for (int c = 1; c <= g.NG && c <= 192; ++c) {
-    const long blocks = (long)((g.NG + c - 1) / c) * g.nseg;
-    const long rounds = (blocks + 255) / 256;
-    const double crossings = H2 % c == 0 ? 0.0 : (c % H2 == 0 ? c / H2 - 1 : (double)c / H2);
-    const double cost = rounds * (c + 1.0 + 0.3 * crossings);
-    if (cost < best) { best = cost; g.gpc = c; }
-  }
+  // chunks: whole rounds of 256 workgroups, start-up + plane-pair crossings as in plan_conv_tapdh
+  g.gpc = chunk_groups_by_rounds(g.NG, g.nseg, g.H / 2, 192, 1.0, 0.3);
   if (const char* e = ssbev_tune("SSBEV_WGRAD_DH_GPC")) { const int v = atoi(e); if (v > 0) g.gpc = v; }   // tuning hook
   p.nchunks = ((g.NG + g.gpc - 1) / g.gpc) * g.nseg;
   p.ok = true;
@@ -4167,8 +4176,7 @@ int run_wgrad_dh(const float* x, const float* gy, float* gw, const WgradDhPlan& 
   return ssbev_launch_status();
 }
 
-int launch_conv_taph(const float* x, const float* wp, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
-                     hipStream_t st) {
+ConvTapGeom plan_conv_taph(const ssbev_conv_dims* d, int mode) {
   ConvTapGeom g;
   g.B = d->B; g.D = d->Do; g.H = d->Ho; g.W = d->Wo;
   g.K = mode == 0 ? d->Cin : d->Cout;
@@ -4176,26 +4184,24 @@ int launch_conv_taph(const float* x, const float* wp, const float* bias, float* 
   g.nseg = (g.W + kTapWseg - 1) / kTapWseg;
   g.NG = g.B * g.D * (g.H / 2);              // row pairs
   g.relu = mode == 0 ? d->relu : 0;
-  g.has_bias = (mode == 0 && bias) ? 1 : 0;
+  g.has_bias = 0;
   g.accumulate = d->accumulate;
   // One 512-thread workgroup per CU (141 KB of LDS).  Chunk length (row pairs per workgroup) by a small cost model fitted on
   // the 192 x 48 x 160 layer (tools/taph_gpc_probe.py): whole rounds of 256 workgroups matter most (the last round's idle
   // CUs: 12 pairs -> 7.5 rounds 0.580 ms, 18 pairs -> 5.0 rounds 0.537 ms), then the start-up of a chunk (weights + first
   // four rows, ~0.6 pair) and the ring restage at every depth-plane crossing (~0.3 pair)
-  const int H2 = g.H / 2;
-  double best = 1e30;
-  g.gpc = 1;
-  for (int c = 1; c <= g.NG && c <= 96; ++c) {
-    const long blocks = (long)((g.NG + c - 1) / c) * g.nseg;
-    const long rounds = (blocks + 255) / 256;
-    const double crossings = H2 % c == 0 ? 0.0 : (c % H2 == 0 ? c / H2 - 1 : (double)c / H2);
-    const double cost = rounds * (c + 0.6 + 0.3 * crossings);
-    if (cost < best) { best = cost; g.gpc = c; }
-  }
+  g.gpc = chunk_groups_by_rounds(g.NG, g.nseg, g.H / 2, 96, 0.6, 0.3);
   if (const char* e = ssbev_tune("SSBEV_TAPH_GPC")) { const int v = atoi(e); if (v > 0) g.gpc = v; }   // tuning hook
   // (Round 3 built a plane-aligned chunk order -- XCD x owns 24 consecutive planes, plane index fastest, so that the chunks of
   // d - 1, d, d + 1 meet in one L2: 572 -> 228 MB of HBM reads per launch, but the workgroups moving in step cost the kernel
   // 8 % (0.533 -> 0.579 ms, profiles/r3y_taph_plane_aligned.txt).  The kernel is not HBM-bound; removed in round 6.)
+  return g;
+}
+
+int launch_conv_taph(const float* x, const float* wp, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
+                     hipStream_t st) {
+  ConvTapGeom g = plan_conv_taph(d, mode);
+  g.has_bias = (mode == 0 && bias) ? 1 : 0;
   const long nranges = (g.NG + g.gpc - 1) / g.gpc;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_taph_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)kTwLdsBytes) != hipSuccess)
@@ -4205,8 +4211,7 @@ int launch_conv_taph(const float* x, const float* wp, const float* bias, float* 
   return ssbev_launch_status();
 }
 
-int launch_conv_tap(const float* x, const float* wp, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
-                    hipStream_t st) {
+ConvTapGeom plan_conv_tap(const ssbev_conv_dims* d, int mode) {
   ConvTapGeom g;
   g.B = d->B; g.D = d->Do; g.H = d->Ho; g.W = d->Wo;
   g.K = mode == 0 ? d->Cin : d->Cout;
@@ -4214,7 +4219,7 @@ int launch_conv_tap(const float* x, const float* wp, const float* bias, float* y
   g.nseg = (g.W + kTapWseg - 1) / kTapWseg;
   g.NG = g.B * g.D * g.H;
   g.relu = mode == 0 ? d->relu : 0;
-  g.has_bias = (mode == 0 && bias) ? 1 : 0;
+  g.has_bias = 0;
   g.accumulate = d->accumulate;
   // two workgroups per CU; whole rounds of 512 workgroups, >= 16 rows each
   long nranges = 512 / g.nseg;
@@ -4224,7 +4229,14 @@ int launch_conv_tap(const float* x, const float* wp, const float* bias, float* y
   }
   if (nranges < 1) nranges = 1;
   g.gpc = (int)((g.NG + nranges - 1) / nranges);
-  nranges = (g.NG + g.gpc - 1) / g.gpc;
+  return g;
+}
+
+int launch_conv_tap(const float* x, const float* wp, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
+                    hipStream_t st) {
+  ConvTapGeom g = plan_conv_tap(d, mode);
+  g.has_bias = (mode == 0 && bias) ? 1 : 0;
+  const long nranges = (g.NG + g.gpc - 1) / g.gpc;
   auto kern = d->precision == 1 ? conv_tap_kernel<true> : conv_tap_kernel<false>;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)kTapLdsBytes) != hipSuccess)
@@ -4363,6 +4375,26 @@ int ssbev_conv_kernel_class(const ssbev_conv_dims* d, int mode) {
     if (g.Cin % 4 == 0 && conv_igemm_applicable(g)) return 11;
   }
   return 0;
+}
+
+int ssbev_conv_chunk_groups(const ssbev_conv_dims* d, int mode) {
+  if (!conv_dims_ok(d) || mode < 0 || mode > 2) return 0;
+  if (mode == 2) {                                            // the order of ssbev_conv_bwd_weight
+    if (ssbev_bf16::storage_mode(d) || ssbev_thin::wgrad_applicable(d) || plan_wgrad_thin(d).ok) return 0;
+    if (plan_wgrad_1x1(d).ok && d->tile_hint != 7) return 0;
+    const WgradDhPlan hp = plan_wgrad_dh(d);
+    return hp.ok ? hp.g.gpc : 0;
+  }
+  switch (ssbev_conv_kernel_class(d, mode)) {
+    case 1: return plan_conv_tap(d, mode).gpc;
+    case 2: return plan_conv_taph(d, mode).gpc;
+    case 3: return plan_conv_thin(d, mode).gpc;
+    case 7: return plan_conv_tap2(d, mode).gpc;
+    case 8: return plan_conv_tap2up(d, mode).gpc;
+    case 9: return plan_conv_tapdh(d, mode).gpc;
+    case 17: return ssbev_bf16::tap_chunk_groups(d, mode);
+    default: return 0;
+  }
 }
 
 size_t ssbev_conv_packed_weight_elems(const ssbev_conv_dims* d) {

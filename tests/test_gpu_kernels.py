@@ -865,11 +865,25 @@ def test_deform_conv_vs_oracle(cfg):
 @pytest.mark.parametrize("hint", [9, 6])
 def test_conv_tap_split_lds_kernel(case, hint):
     """The register-weights / LDS-rows kernels of the <= 32-channel 3x3x3 layers (forced with a tile hint) against ATen,
-    forward and data gradient; the weight gradient of the same call runs on its usual kernels.  Hint 9: the library's
-    choice -- conv_taph_kernel (Winograd F(2,3) along h inside the tap walk) when H is even, conv_tap_kernel otherwise;
-    hint 6: always conv_tap_kernel.  Cases with <= 4 channels on the output side of a pass take the thin VALU kernels
-    (conv_thin_kernel / wgrad_thin_kernel) instead."""
+    forward and data gradient; the weight gradient of the same call runs on its usual kernels (wgrad_tapdh_kernel under hint 9
+    when D and H are even and both sides have >= 16 / >= 8 channels).  Hint 9: the library's choice -- conv_tapdh_kernel
+    (Winograd F(2,3) along d and h inside the tap walk, class 9) when D and H are even, conv_taph_kernel (F(2,3) along h,
+    class 2) when only H is, conv_tap_kernel (class 1) otherwise; a pass with <= 4 channels on its output side and >= 16 on
+    its input side takes the thin VALU kernel (conv_thin_kernel, class 3; wgrad_thin_kernel) instead.  Hint 6: always
+    conv_tap_kernel.  The kernel class of either pass is asserted.  All of these launches walk ONE row group per chunk; the
+    multi-block walks are test_gpu_conv_walks.py's."""
     B, Cin, Cout, D, H, W, has_bias = case
+    # the dims the operator hands to the library: the K-role channel count of a pass is padded to a multiple of 4
+    Kf, Kb = Cin + (-Cin) % 4, Cout + (-Cout) % 4
+    for mode, K, N in ((0, Kf, Cout), (1, Kb, Kf)):
+        if hint == 6:
+            expect = 1
+        elif N <= 4 and K >= 16:
+            expect = 3
+        else:
+            expect = 9 if (D % 2 == 0 and H % 2 == 0) else 2 if H % 2 == 0 else 1
+        d = capi.ConvDims(B, Kf, Cout if mode == 0 else Kb, D, H, W, D, H, W, 3, 3, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, hint, 0)
+        assert capi.load().ssbev_conv_kernel_class(F.C.byref(d), mode) == expect, (mode, expect)
     x = S.hash_normal(f"tap/x{case}", (B, Cin, D, H, W))
     w = S.hash_uniform(f"tap/w{case}", (Cout, Cin, 3, 3, 3), -1, 1) * (3.0 / (Cin * 27)) ** 0.5
     b = S.hash_uniform(f"tap/b{case}", (Cout,), -0.5, 0.5) if has_bias else None
@@ -917,16 +931,21 @@ def test_conv_thin_side_layers_mfma_kernels(case):
 
 
 def test_conv_tap_winograd_h_full_size_agrees_with_plain_tap_kernels():
-    """BASELINE-size check of the in-kernel F(2,3)-along-h kernels (conv_taph_kernel, wgrad_lds_kernel<..., WINO>): the
-    32 -> 32 cost-volume layer at 192 x 48 x 160 (kitti_d192, too large for the CPU reference in a test) against the plain
-    tap kernels (tile hint 6, themselves pinned to ATen at small sizes above) -- forward, data gradient, weight gradient."""
+    """BASELINE-size check of the in-kernel Winograd walks: the 32 -> 32 cost-volume layer at 192 x 48 x 160 (kitti_d192, too
+    large for the CPU reference in a test) against the plain tap kernels (tile hint 6: conv_tap_kernel and wgrad_lds_kernel,
+    themselves pinned to ATen at small sizes above) -- forward, data gradient, weight gradient.  Hint 0 is the library's choice,
+    conv_tapdh_kernel + wgrad_tapdh_kernel (F(2,3) along d and h); hint 4 keeps the F(2,3)-along-h kernels (conv_taph_kernel,
+    wgrad_lds_kernel<..., WINO>); hint 5 is conv_tapdh_kernel with the weight-gradient variant that has a run-time k-step count."""
     D, H, W = 192, 48, 160
     x = S.hash_normal("taph/x", (1, 32, D, H, W)).to(DEV)
     w = (S.hash_uniform("taph/w", (32, 32, 3, 3, 3), -1, 1) * (3.0 / (32 * 27)) ** 0.5).to(DEV)
     b = S.hash_uniform("taph/b", (32,), -0.5, 0.5).to(DEV)
     go = S.hash_normal("taph/go", (1, 32, D, H, W)).to(DEV)
     res = []
-    for hint in (6, 0, 5):          # 5: the weight-gradient variant with a run-time k-step count
+    lib = capi.load()
+    for hint, cls in ((6, 1), (0, 9), (4, 2), (5, 9)):
+        d = capi.ConvDims(1, 32, 32, D, H, W, D, H, W, 3, 3, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, hint, 0)
+        assert lib.ssbev_conv_kernel_class(F.C.byref(d), 0) == cls and lib.ssbev_conv_kernel_class(F.C.byref(d), 1) == cls
         F.TILE_HINT = hint
         try:
             xg, wg = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
