@@ -701,6 +701,24 @@ int ssbev_gemm_nt(const float* A, const float* W, const float* bias, float* C, c
 size_t ssbev_gemm_tn_workspace(const ssbev_gemm_dims* d);
 int ssbev_gemm_tn(const float* A, const float* B, float* C, const ssbev_gemm_dims* d, void* workspace, size_t ws_bytes,
                   ssbev_stream_t stream);
+/* Host-side plan query (since ssbev_version() 106; no device work): the kernel, tile and chunking a launch of these dims uses,
+ * from the plan function the launchers and the *_workspace queries themselves read.  form: 0 NN, 1 NT, 2 TN.  SSBEV_EINVAL for
+ * dims the matching entry point refuses (d2s dims are answered like any other).
+ * kernel codes --
+ *   NN / NT: the tile configuration of gemm_nn_kernel: 0 = 128 x 128, 1 = 128 x 64, 2 = 192 x 128 (96-row wave tiles),
+ *            3 = 128 x 160 (four waves stacked along M), 4 = 128 x 128 with 16-deep k stages (tuning builds only);
+ *   TN:      10 = gemm_tn_kernel<1> (128 k x 64 n), 11 = gemm_tn_kernel<2> (128 x 128), 12 = gemm_tn_kernel<5, 1, 1> (128 x 160);
+ *   skinny TN (gemm_tn_skinny_kernel<KT, NT, QUAD> + gemm_sum_wide_kernel): 20 = <1, 1>, 21 = <1, 2>, 22 = <2, 1>, 23 = <2, 2>,
+ *            24 = <2, 2, quad>. */
+typedef struct {
+  int kernel;      /* see above */
+  int bm, bn, bk;  /* workgroup tile (TN: k rows x n columns x 32 reduction rows; skinny: the tile a workgroup holds x 16 rows per step) */
+  int nchunk;      /* split-K chunks (NN / NT), row chunks (TN), workgroups per batch element (skinny TN) */
+  int per_chunk;   /* k stages per chunk (NN / NT), rows per chunk (TN), rows per run of a wave (skinny: 4 nchunk runs, quad: nchunk) */
+  int64_t grid;    /* workgroups of the main launch */
+  size_t workspace;/* bytes, what the form's *_workspace function returns */
+} ssbev_gemm_plan;
+int ssbev_gemm_plan_query(const ssbev_gemm_dims* d, int form, ssbev_gemm_plan* out);
 
 /* Depth-fused Winograd contraction (csrc/winograd_fused.hip): F(4,3) x F(4,3) over (h, w) in memory (P / Mo / Z are
  * [36][B*D*(H/4)*(W/4)][C], the 2-D transforms above with D as a batch axis), F(2,3) along d in registers around the MFMAs.

@@ -99,6 +99,11 @@ class GemmDims(C.Structure):
                 ("ep_mul", C.c_void_p), ("ep_rowsub", C.c_void_p)]
 
 
+class GemmPlan(C.Structure):
+    _fields_ = [("kernel", C.c_int), ("bm", C.c_int), ("bn", C.c_int), ("bk", C.c_int), ("nchunk", C.c_int), ("per_chunk", C.c_int),
+                ("grid", C.c_int64), ("workspace", C.c_size_t)]
+
+
 class JitterParams(C.Structure):
     _fields_ = [("flags", C.c_int), ("mode", C.c_int), ("delta", C.c_float), ("alpha", C.c_float), ("saturation", C.c_float),
                 ("hue", C.c_float), ("perm", C.c_int * 3)]
@@ -209,6 +214,7 @@ SIGNATURES = {
     "ssbev_gemm_nt": (C.c_int, [_P, _P, _P, _P, C.POINTER(GemmDims), _P, C.c_size_t, _P]),
     "ssbev_gemm_tn_workspace": (C.c_size_t, [C.POINTER(GemmDims)]),
     "ssbev_gemm_tn": (C.c_int, [_P, _P, _P, C.POINTER(GemmDims), _P, C.c_size_t, _P]),
+    "ssbev_gemm_plan_query": (C.c_int, [C.POINTER(GemmDims), C.c_int, C.POINTER(GemmPlan)]),
     "ssbev_wino43_df_supported": (C.c_int, [C.POINTER(WinoDims), C.c_int]),
     "ssbev_wino43_df_instance": (C.c_int, [C.POINTER(WinoDims), C.c_int]),
     "ssbev_wino43_df_packed_elems": (C.c_size_t, [C.c_int, C.c_int]),

@@ -672,11 +672,90 @@ int nn_pick_cfg(const ssbev_gemm_dims* d, int* nchunk_out) {
   return cfg;
 }
 
+// ---- the launch plan: ONE function per form decides kernel, tile, chunking, grid and workspace; the launchers, the
+// *_workspace queries and ssbev_gemm_plan_query all read it (kernel codes: ssbev_gemm_plan in ssbev.h)
+enum { kTnNarrow = 10, kTnPlain = 11, kTnWide = 12, kTnSkinny11 = 20, kTnSkinny12 = 21, kTnSkinny21 = 22, kTnSkinny22 = 23,
+       kTnSkinnyQuad = 24 };
+
+struct LaunchPlan {
+  ssbev_gemm_plan p;
+  int mblocks, nblocks;
+};
+
 template <bool BT>
-size_t nn_workspace(const ssbev_gemm_dims* d) {
+LaunchPlan plan_nn(const ssbev_gemm_dims* d) {
+  LaunchPlan pl;
   int nchunk;
-  nn_pick_cfg<BT>(d, &nchunk);
-  return nchunk > 1 ? (size_t)nchunk * d->batch * d->M * d->N * sizeof(float) : 0;
+  const int cfg = nn_pick_cfg<BT>(d, &nchunk);
+  const NnCfg& c = kNnCfgs[cfg];
+  pl.mblocks = (d->M + c.bm - 1) / c.bm;
+  pl.nblocks = (d->N + c.bn - 1) / c.bn;
+  const int nst = (d->K + c.bk - 1) / c.bk;
+  pl.p.kernel = cfg;
+  pl.p.bm = c.bm; pl.p.bn = c.bn; pl.p.bk = c.bk;
+  pl.p.nchunk = nchunk;
+  pl.p.per_chunk = (nst + nchunk - 1) / nchunk;               // k stages per chunk
+  pl.p.grid = (int64_t)d->batch * nchunk * pl.mblocks * pl.nblocks;
+  pl.p.workspace = nchunk > 1 ? (size_t)nchunk * d->batch * d->M * d->N * sizeof(float) : 0;
+  return pl;
+}
+
+// TN: the skinny streaming kernels (K, N <= 128 under a very long row reduction) or the tiled kernel over row chunks
+bool tn_skinny(const ssbev_gemm_dims* d) { return d->K <= 128 && d->N <= 128 && d->M >= 32768 && d->d2s_kd == 0; }
+bool tn_quad(const ssbev_gemm_dims* d) { return d->K > 64 || d->N > 64; }
+int tn_skinny_wgs(const ssbev_gemm_dims* d) {
+  // ~2 workgroups per CU (8 waves streaming per CU), at least 256 rows per run
+  const long runs = tn_quad(d) ? 512 : 2048;
+  const long w = std::min<long>(runs, std::max<long>(4, d->M / 256));
+  return tn_quad(d) ? (int)w : (int)((w + 3) / 4);
+}
+
+LaunchPlan plan_tn(const ssbev_gemm_dims* d) {
+  LaunchPlan pl;
+  if (tn_skinny(d)) {
+    const int wgs = tn_skinny_wgs(d);
+    const bool quad = tn_quad(d);
+    const long runs = quad ? wgs : (long)wgs * 4;
+    const int kt = quad ? 2 : (d->K + 31) / 32, nt = quad ? 2 : (d->N + 31) / 32;
+    pl.mblocks = pl.nblocks = 1;
+    pl.p.kernel = quad ? kTnSkinnyQuad : (kt == 1 ? (nt == 1 ? kTnSkinny11 : kTnSkinny12) : (nt == 1 ? kTnSkinny21 : kTnSkinny22));
+    pl.p.bm = (quad ? 64 : 32) * kt; pl.p.bn = (quad ? 64 : 32) * nt; pl.p.bk = 16;       // 8 row pairs in flight per wave
+    pl.p.nchunk = wgs;                                                                     // one partial per workgroup
+    pl.p.per_chunk = (int)(((long)d->M + runs - 1) / runs + 1) / 2 * 2;                    // rows per run (even: row pairs)
+    pl.p.grid = (int64_t)wgs * d->batch;
+    pl.p.workspace = (size_t)wgs * d->batch * d->K * d->N * sizeof(float);
+    return pl;
+  }
+  const int wn = pick_wn(d->N, d->d2s_kd > 0 ? d->d2s_Co : 0);
+  const bool wide = tn_wide(d);
+  const int BN = wide ? 160 : 64 * wn;
+  pl.mblocks = (d->K + 127) / 128;
+  pl.nblocks = (d->N + BN - 1) / BN;
+  const int tiles = pl.mblocks * pl.nblocks;
+  const int nchunk = d->ep_mul ? 1 : (wide ? tn_chunks_model(d, tiles) : tn_chunks(d, tiles));      // the fused epilogue needs the complete row reduction
+  pl.p.kernel = wide ? kTnWide : (wn == 2 ? kTnPlain : kTnNarrow);
+  pl.p.bm = 128; pl.p.bn = BN; pl.p.bk = 32;
+  pl.p.nchunk = nchunk;
+  pl.p.per_chunk = ((d->M + nchunk - 1) / nchunk + 31) / 32 * 32;
+  pl.p.grid = (int64_t)d->batch * nchunk * tiles;
+  pl.p.workspace = nchunk > 1 ? (size_t)nchunk * d->batch * d->K * d->N * sizeof(float) : 0;
+  return pl;
+}
+
+// what the entry points refuse on the dims alone (operand pointers apart): shared with ssbev_gemm_plan_query
+bool nn_dims_ok(const ssbev_gemm_dims* d) {
+  if (!gemm_ok(d) || d->lda < d->K || d->ldb < d->N) return false;
+  return d->d2s_kd > 0 ? (d->batch == 1 && d->N == d->d2s_kd * d->d2s_kh * d->d2s_kw * d->d2s_Co) : d->ldc >= d->N;
+}
+bool nt_dims_ok(const ssbev_gemm_dims* d) {
+  if (!gemm_ok(d) || d->ldb < d->K || d->ldc < d->N) return false;
+  return d->d2s_kd > 0 ? (d->batch == 1 && d->K == d->d2s_kd * d->d2s_kh * d->d2s_kw * d->d2s_Co) : d->lda >= d->K;
+}
+bool tn_dims_ok(const ssbev_gemm_dims* d) {
+  if (!gemm_ok(d) || d->lda < d->K) return false;
+  if (d->d2s_kd > 0 ? (d->batch != 1 || d->N != d->d2s_kd * d->d2s_kh * d->d2s_kw * d->d2s_Co) : d->ldb < d->N) return false;
+  if ((d->ep_mul != nullptr) != (d->ep_rowsub != nullptr)) return false;
+  return !(d->ep_mul && (tn_skinny(d) || d->d2s_kd > 0));
 }
 
 template <bool BT>
@@ -684,23 +763,22 @@ int launch_nn(const float* A, const float* B, const float* bias, float* Cm, cons
               hipStream_t st) {
   GemmGeom g;
   fill_geom(g, d);
-  int nchunk;
-  const int cfg = nn_pick_cfg<BT>(d, &nchunk);
+  const LaunchPlan pl = plan_nn<BT>(d);
+  const int cfg = pl.p.kernel;
   const NnCfg& c = kNnCfgs[cfg];
-  g.mblocks = (d->M + c.bm - 1) / c.bm;
-  g.nblocks = (d->N + c.bn - 1) / c.bn;
-  g.nchunk = nchunk;
-  const int nst = (d->K + c.bk - 1) / c.bk;
-  g.rows_per_chunk = (nst + g.nchunk - 1) / g.nchunk;         // k stages per chunk
+  g.mblocks = pl.mblocks;
+  g.nblocks = pl.nblocks;
+  g.nchunk = pl.p.nchunk;
+  g.rows_per_chunk = pl.p.per_chunk;                          // k stages per chunk
   float* dst = Cm;
   const float* kbias = bias;
   if (g.nchunk > 1) {
-    if (!ws || ws_bytes < nn_workspace<BT>(d)) return SSBEV_EWORKSPACE;
+    if (!ws || ws_bytes < pl.p.workspace) return SSBEV_EWORKSPACE;
     dst = static_cast<float*>(ws);
     g.ldc = d->N; g.sc = (long)d->M * d->N; g.relu = 0;
     kbias = nullptr;
   }
-  const long nwg = (long)g.batch * g.nchunk * g.mblocks * g.nblocks;
+  const long nwg = (long)pl.p.grid;
   const size_t lds = (size_t)2 * (c.bm * c.bk + c.bk * c.bn) * sizeof(float);
   constexpr int DM = BT ? 2 : 1;          // what d2s means for this form
 #define SSBEV_GEMM_LAUNCH(...)                                                                                             \
@@ -750,13 +828,12 @@ int ssbev_gemm_d2s_rowoff(int64_t* rowoff, int M, int D, int H, int W, int kd, i
 // strides in floats (sb = 0: one B for every batch).  K, N, lda, ldb multiples of 4 (16-byte LDS-DMA granules).
 // d2s set: the result row m, column (tap, co) is stored at the depth-to-space position of the fine grid (ldc / sc unused,
 // C = the fine tensor of batch element b = 0; bias indexed by co).
-size_t ssbev_gemm_nn_workspace(const ssbev_gemm_dims* d) { return gemm_ok(d) ? nn_workspace<false>(d) : 0; }
-size_t ssbev_gemm_nt_workspace(const ssbev_gemm_dims* d) { return gemm_ok(d) ? nn_workspace<true>(d) : 0; }
+size_t ssbev_gemm_nn_workspace(const ssbev_gemm_dims* d) { return gemm_ok(d) ? plan_nn<false>(d).p.workspace : 0; }
+size_t ssbev_gemm_nt_workspace(const ssbev_gemm_dims* d) { return gemm_ok(d) ? plan_nn<true>(d).p.workspace : 0; }
 
 int ssbev_gemm_nn(const float* A, const float* B, const float* bias, float* Cm, const ssbev_gemm_dims* d, void* ws, size_t ws_bytes,
                   ssbev_stream_t stream) {
-  if (!gemm_ok(d) || !A || !B || !Cm || d->lda < d->K || d->ldb < d->N) return SSBEV_EINVAL;
-  if (d->d2s_kd > 0 ? (d->batch != 1 || d->N != d->d2s_kd * d->d2s_kh * d->d2s_kw * d->d2s_Co) : d->ldc < d->N) return SSBEV_EINVAL;
+  if (!nn_dims_ok(d) || !A || !B || !Cm) return SSBEV_EINVAL;
   return launch_nn<false>(A, B, bias, Cm, d, ws, ws_bytes, as_stream(stream));
 }
 
@@ -764,84 +841,53 @@ int ssbev_gemm_nn(const float* A, const float* B, const float* bias, float* Cm, 
 // d2s set: row m of A is GATHERED from the fine grid (K = taps * Co wide; lda / sa unused, batch = 1).
 int ssbev_gemm_nt(const float* A, const float* W, const float* bias, float* Cm, const ssbev_gemm_dims* d, void* ws, size_t ws_bytes,
                   ssbev_stream_t stream) {
-  if (!gemm_ok(d) || !A || !W || !Cm || d->ldb < d->K || d->ldc < d->N) return SSBEV_EINVAL;
-  if (d->d2s_kd > 0 ? (d->batch != 1 || d->K != d->d2s_kd * d->d2s_kh * d->d2s_kw * d->d2s_Co) : d->lda < d->K) return SSBEV_EINVAL;
+  if (!nt_dims_ok(d) || !A || !W || !Cm) return SSBEV_EINVAL;
   return launch_nn<true>(A, W, bias, Cm, d, ws, ws_bytes, as_stream(stream));
 }
 
 // C[b][k][n] = sum_r A[b][r][k] B[b][r][n]: d->M = rows (the reduction), d->K x d->N the dense result (ldc = N).
 // d2s set: row r of B is gathered from the fine grid (N = taps * Co wide).  Workspace: partial results of the row chunks
 // (ssbev_gemm_tn_workspace bytes; 0 when one chunk suffices), summed in chunk order (deterministic).
-static bool tn_skinny(const ssbev_gemm_dims* d) { return d->K <= 128 && d->N <= 128 && d->M >= 32768 && d->d2s_kd == 0; }
-static bool tn_quad(const ssbev_gemm_dims* d) { return d->K > 64 || d->N > 64; }
-static int tn_skinny_wgs(const ssbev_gemm_dims* d) {
-  // ~2 workgroups per CU (8 waves streaming per CU), at least 256 rows per run
-  const long runs = tn_quad(d) ? 512 : 2048;
-  const long w = std::min<long>(runs, std::max<long>(4, d->M / 256));
-  return tn_quad(d) ? (int)w : (int)((w + 3) / 4);
-}
-
-size_t ssbev_gemm_tn_workspace(const ssbev_gemm_dims* d) {
-  if (!gemm_ok(d)) return 0;
-  if (tn_skinny(d)) return (size_t)tn_skinny_wgs(d) * d->batch * d->K * d->N * sizeof(float);
-  const int wn = pick_wn(d->N, d->d2s_kd > 0 ? d->d2s_Co : 0);
-  const bool wide = tn_wide(d);
-  const int tiles = ((d->K + 127) / 128) * (wide ? (d->N + 159) / 160 : (d->N + 64 * wn - 1) / (64 * wn));
-  const int nchunk = d->ep_mul ? 1 : (wide ? tn_chunks_model(d, tiles) : tn_chunks(d, tiles));
-  return nchunk > 1 ? (size_t)nchunk * d->batch * d->K * d->N * sizeof(float) : 0;
-}
+size_t ssbev_gemm_tn_workspace(const ssbev_gemm_dims* d) { return gemm_ok(d) ? plan_tn(d).p.workspace : 0; }
 
 int ssbev_gemm_tn(const float* A, const float* B, float* Cm, const ssbev_gemm_dims* d, void* ws, size_t ws_bytes,
                   ssbev_stream_t stream) {
-  if (!gemm_ok(d) || !A || !B || !Cm || d->lda < d->K) return SSBEV_EINVAL;
-  if (d->d2s_kd > 0 ? (d->batch != 1 || d->N != d->d2s_kd * d->d2s_kh * d->d2s_kw * d->d2s_Co) : d->ldb < d->N) return SSBEV_EINVAL;
+  if (!tn_dims_ok(d) || !A || !B || !Cm) return SSBEV_EINVAL;
   GemmGeom g;
   fill_geom(g, d);
   g.ldc = d->N; g.sc = (long)d->K * d->N; g.relu = 0;
   g.ep_mul = d->ep_mul; g.ep_rowsub = d->ep_rowsub;
-  if ((d->ep_mul != nullptr) != (d->ep_rowsub != nullptr)) return SSBEV_EINVAL;
-  if (d->ep_mul && (tn_skinny(d) || d->d2s_kd > 0)) return SSBEV_EINVAL;
-  if (tn_skinny(d)) {
-    if (!ws || ws_bytes < ssbev_gemm_tn_workspace(d)) return SSBEV_EWORKSPACE;
-    const int wgs = tn_skinny_wgs(d);
-    const bool quad = tn_quad(d);
-    const long runs = quad ? wgs : (long)wgs * 4;
-    const int rows_per_run = (int)(((long)d->M + runs - 1) / runs + 1) / 2 * 2;
-    hipStream_t st = as_stream(stream);
+  const LaunchPlan pl = plan_tn(d);
+  if (pl.p.workspace > 0 && (!ws || ws_bytes < pl.p.workspace)) return SSBEV_EWORKSPACE;
+  hipStream_t st = as_stream(stream);
+  if (pl.p.kernel >= kTnSkinny11) {
+    const int wgs = pl.p.nchunk, rows_per_run = pl.p.per_chunk;
     dim3 grid(wgs, d->batch), block(256);
     float* part = static_cast<float*>(ws);
-    if (quad) {
-      hipLaunchKernelGGL((gemm_tn_skinny_kernel<2, 2, true>), grid, block, 0, st, A, B, part, g, rows_per_run);
-    } else {
-      const int kt = (d->K + 31) / 32, nt = (d->N + 31) / 32;
-      if (kt == 1 && nt == 1) hipLaunchKernelGGL((gemm_tn_skinny_kernel<1, 1, false>), grid, block, 0, st, A, B, part, g, rows_per_run);
-      else if (kt == 1) hipLaunchKernelGGL((gemm_tn_skinny_kernel<1, 2, false>), grid, block, 0, st, A, B, part, g, rows_per_run);
-      else if (nt == 1) hipLaunchKernelGGL((gemm_tn_skinny_kernel<2, 1, false>), grid, block, 0, st, A, B, part, g, rows_per_run);
-      else hipLaunchKernelGGL((gemm_tn_skinny_kernel<2, 2, false>), grid, block, 0, st, A, B, part, g, rows_per_run);
+    switch (pl.p.kernel) {
+      case kTnSkinnyQuad: hipLaunchKernelGGL((gemm_tn_skinny_kernel<2, 2, true>), grid, block, 0, st, A, B, part, g, rows_per_run); break;
+      case kTnSkinny11: hipLaunchKernelGGL((gemm_tn_skinny_kernel<1, 1, false>), grid, block, 0, st, A, B, part, g, rows_per_run); break;
+      case kTnSkinny12: hipLaunchKernelGGL((gemm_tn_skinny_kernel<1, 2, false>), grid, block, 0, st, A, B, part, g, rows_per_run); break;
+      case kTnSkinny21: hipLaunchKernelGGL((gemm_tn_skinny_kernel<2, 1, false>), grid, block, 0, st, A, B, part, g, rows_per_run); break;
+      default: hipLaunchKernelGGL((gemm_tn_skinny_kernel<2, 2, false>), grid, block, 0, st, A, B, part, g, rows_per_run); break;
     }
     const size_t n = (size_t)d->batch * d->K * d->N;
     hipLaunchKernelGGL(gemm_sum_wide_kernel, dim3(cdiv(n, 64)), dim3(1024), 0, st, part, Cm, n, wgs);
     return ssbev_launch_status();
   }
-  const int wn = pick_wn(d->N, d->d2s_kd > 0 ? d->d2s_Co : 0);
-  const bool wide = tn_wide(d);
-  const int BN = wide ? 160 : 64 * wn;
-  g.mblocks = (d->K + 127) / 128;
-  g.nblocks = (d->N + BN - 1) / BN;
-  g.nchunk = d->ep_mul ? 1 : (wide ? tn_chunks_model(d, g.mblocks * g.nblocks) : tn_chunks(d, g.mblocks * g.nblocks));      // the fused epilogue needs the complete row reduction
-  g.rows_per_chunk = ((d->M + g.nchunk - 1) / g.nchunk + 31) / 32 * 32;
-  if (g.nchunk > 1 && (!ws || ws_bytes < ssbev_gemm_tn_workspace(d))) return SSBEV_EWORKSPACE;
+  g.mblocks = pl.mblocks;
+  g.nblocks = pl.nblocks;
+  g.nchunk = pl.p.nchunk;
+  g.rows_per_chunk = pl.p.per_chunk;
   float* dst = g.nchunk > 1 ? static_cast<float*>(ws) : Cm;
-  const long nwg = (long)g.batch * g.nchunk * g.mblocks * g.nblocks;
-  const size_t lds = (size_t)2 * (32 * 128 + 32 * BN) * sizeof(float);       // 64 / 48 KiB
-  hipStream_t st = as_stream(stream);
-  if (wide) {
+  const long nwg = (long)pl.p.grid;
+  const size_t lds = (size_t)2 * (32 * 128 + 32 * pl.p.bn) * sizeof(float);       // 72 / 64 / 48 KiB
+  if (pl.p.kernel == kTnWide) {
     auto kern = gemm_tn_kernel<5, 1, 1>;
-    const size_t ldsw = (size_t)2 * (32 * 128 + 32 * 160) * sizeof(float);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw) != hipSuccess)
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return SSBEV_ELAUNCH;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), ldsw, st, A, B, dst, g);
-  } else if (wn == 2) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), lds, st, A, B, dst, g);
+  } else if (pl.p.kernel == kTnPlain) {
     auto kern = gemm_tn_kernel<2>;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return SSBEV_ELAUNCH;
@@ -854,6 +900,18 @@ int ssbev_gemm_tn(const float* A, const float* B, float* Cm, const ssbev_gemm_di
     hipLaunchKernelGGL(gemm_sum_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, dst, Cm, n, g.nchunk, (const float*)nullptr, 1, 0);
   }
   return ssbev_launch_status();
+}
+
+// The plan a launch of these dims uses (form 0 NN, 1 NT, 2 TN), from the plan function the launcher itself reads.  No device
+// work; SSBEV_EINVAL for dims the matching entry point refuses.
+int ssbev_gemm_plan_query(const ssbev_gemm_dims* d, int form, ssbev_gemm_plan* out) {
+  if (!out) return SSBEV_EINVAL;
+  switch (form) {
+    case 0: if (!nn_dims_ok(d)) return SSBEV_EINVAL; *out = plan_nn<false>(d).p; return SSBEV_OK;
+    case 1: if (!nt_dims_ok(d)) return SSBEV_EINVAL; *out = plan_nn<true>(d).p; return SSBEV_OK;
+    case 2: if (!tn_dims_ok(d)) return SSBEV_EINVAL; *out = plan_tn(d).p; return SSBEV_OK;
+    default: return SSBEV_EINVAL;
+  }
 }
 
 }  // extern "C"
