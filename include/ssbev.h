@@ -345,6 +345,29 @@ int ssbev_groupnorm2_bwd_ext(const float* gy, const uint64_t* relu_mask, const f
                              const ssbev_norm2_dims* d, const ssbev_norm2_ext* ext, void* ws, size_t ws_bytes,
                              ssbev_stream_t stream);
 
+/* Host-side plan query (since ssbev_version() 107; no device work): the geometry a launch of these dims runs with, from the
+ * functions the launchers and the *_workspace queries themselves call.  Exactly one of `d` (ssbev_groupnorm_*) and `d2`
+ * (ssbev_groupnorm2_*) is given.  16-byte bf16 lanes need 16-byte aligned tensors; the entry points look at their pointers,
+ * the query takes `aligned16` (non-zero: every tensor pointer of the call is 16-byte aligned) in their place.  SSBEV_EINVAL for
+ * dims the entry points refuse.
+ * The statistics kernels run a grid of chunks x B x slabs workgroups of 256 threads: a workgroup covers `chunk_len` voxels (the
+ * last chunk of a sample what is left) and a slab of `slab_q` lanes of `vw` channels (the last slab what is left), 256 / lanes
+ * voxels per trip.  The apply kernels run `blocks` workgroups of 256 threads, one lane of 4 channels per thread and trip. */
+typedef struct {
+  int vw;              /* channels per lane of the statistics passes: 4, or 8 (bf16, C % 8 == 0, aligned rows) */
+  int slab_q;          /* lanes per channel slab */
+  int slabs;           /* channel slabs */
+  int chunks;          /* voxel chunks per sample (a batch-statistics side of the two-norm operator: of the folded B * S voxels) */
+  int64_t chunk_len;   /* voxels per chunk */
+  int64_t blocks;      /* workgroups of the apply passes */
+  int fixed;           /* 1: blocks * 256 is a multiple of C / 4, so a thread keeps its channels over its grid-stride trips */
+  int chunks_b;        /* two-norm operator: chunks / chunk_len above are side a's forward statistics, these are side b's */
+  int64_t chunk_len_b;
+  int chunks2;         /* two-norm operator: chunks per sample and voxels per chunk of the backward partial sums (one slab) */
+  int64_t chunk_len2;
+} ssbev_groupnorm_plan;
+int ssbev_groupnorm_plan_query(const ssbev_norm_dims* d, const ssbev_norm2_dims* d2, int aligned16, ssbev_groupnorm_plan* out);
+
 /* ------------------------------------------------------------------------------------------
  * Trilinear x2 upsample (align_corners=False) of channels-last volumes, forward and gather-form
  * backward.  Replaces F.interpolate(..., mode='trilinear') at occhead.py:293-294 and

@@ -99,6 +99,12 @@ class GemmDims(C.Structure):
                 ("ep_mul", C.c_void_p), ("ep_rowsub", C.c_void_p)]
 
 
+class GroupnormPlan(C.Structure):
+    _fields_ = [("vw", C.c_int), ("slab_q", C.c_int), ("slabs", C.c_int), ("chunks", C.c_int), ("chunk_len", C.c_int64),
+                ("blocks", C.c_int64), ("fixed", C.c_int), ("chunks_b", C.c_int), ("chunk_len_b", C.c_int64), ("chunks2", C.c_int),
+                ("chunk_len2", C.c_int64)]
+
+
 class GemmPlan(C.Structure):
     _fields_ = [("kernel", C.c_int), ("bm", C.c_int), ("bn", C.c_int), ("bk", C.c_int), ("nchunk", C.c_int), ("per_chunk", C.c_int),
                 ("grid", C.c_int64), ("workspace", C.c_size_t)]
@@ -172,6 +178,7 @@ SIGNATURES = {
     "ssbev_groupnorm2_workspace": (C.c_size_t, [C.POINTER(Norm2Dims)]),
     "ssbev_groupnorm2_fwd": (C.c_int, [_P] * 12 + [C.POINTER(Norm2Dims), _P, C.c_size_t, _P]),
     "ssbev_groupnorm2_bwd": (C.c_int, [_P] * 16 + [C.POINTER(Norm2Dims), _P, C.c_size_t, _P]),
+    "ssbev_groupnorm_plan_query": (C.c_int, [C.POINTER(NormDims), C.POINTER(Norm2Dims), C.c_int, C.POINTER(GroupnormPlan)]),
     "ssbev_trilinear2x_fwd": (C.c_int, [_P, _P, C.POINTER(UpsampleDims), _P]),
     "ssbev_trilinear2x_bwd": (C.c_int, [_P, _P, C.POINTER(UpsampleDims), _P]),
     "ssbev_dcn_im2col": (C.c_int, [_P, _P, _P, C.POINTER(DcnDims), _P]),

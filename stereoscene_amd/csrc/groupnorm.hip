@@ -420,6 +420,10 @@ __device__ __forceinline__ void relu_mask_apply4(const unsigned long long* __res
 // Sample index of lane-vector i along a grid-stride walk: one 64-bit division per THREAD instead of one per step (round 5: the
 // division was ~60 VALU instructions in front of every 8 / 16 bytes -- the bf16 apply passes, with twice the elements per byte,
 // were VALU-bound on it: 42 / 60 us where the fp32 passes take 29 / 36 us for the same bytes).
+// A thread keeps its channels for the whole grid-stride walk when the stride is a multiple of the lanes per voxel (apply_blocks
+// rounds the grid for that); ssbev_groupnorm_plan_query reports the same predicate on the grid it computes.
+__host__ __device__ __forceinline__ bool apply_fixed(long stride, int q) { return stride % q == 0; }
+
 struct SampleWalk {
   long per, rem;
   int b;
@@ -442,7 +446,7 @@ gn_apply_fwd_kernel(const T* __restrict__ x, const float* __restrict__ gamma, co
   constexpr bool FOLD = sizeof(T) == 2;
   const int q = g.C / VW, cpg = g.C / g.G;
   const long stride = (long)gridDim.x * NT;
-  const bool fixed = stride % q == 0;            // see gn_apply_bwd_kernel
+  const bool fixed = apply_fixed(stride, q);     // see gn_apply_bwd_kernel
   long i = (long)blockIdx.x * NT + threadIdx.x;
   int c = (int)(i % q) * VW, bcur = -1;
   float gam[VW], bet[VW], mu[VW], rs[VW];
@@ -569,7 +573,7 @@ gn_apply_bwd_kernel(const T* __restrict__ gy, const T* __restrict__ x, const T* 
   // the launch makes `stride` a multiple of q whenever it can: a thread then always owns the same channels and
   // the per-channel / per-group constants leave the streaming loop
   constexpr bool FOLD = sizeof(T) == 2;          // bf16 tensors: folded constants, see gn_apply_fwd_kernel
-  const bool fixed = stride % q == 0;
+  const bool fixed = apply_fixed(stride, q);
   long i = (long)blockIdx.x * NT + threadIdx.x;
   int c = (int)(i % q) * VW, bcur = -1;
   float gam[VW], mu[VW], rs[VW], c0[VW], c1[VW];
@@ -671,6 +675,17 @@ bool gn_ok(const ssbev_norm_dims* d) {
 // waves in flight -- and stay at 4.  The ReLU bit mask has ONE layout, per channel quad, read by both widths.)
 int gn_vw(int io_dtype, int C) { return (io_dtype == 1 && C % 8 == 0) ? 8 : 4; }
 
+// 16-byte lanes of bf16 tensors need 16-byte aligned rows: row strides here, base pointers in the entry points
+bool gn_ld16(const ssbev_norm_dims* d) {
+  return !((d->ld_y != 0 && d->ld_y % 8 != 0) || (d->ld_gy != 0 && d->ld_gy % 8 != 0));
+}
+// the lane width a statistics launch really runs with (`aligned16`: every tensor pointer it reads is 16-byte aligned).  The
+// channel slabs stay those of gn_vw (make_geom): a bf16 problem that falls back to 4 channels per lane has twice the slabs.
+int gn_stat_vw(const ssbev_norm_dims* d, bool aligned16) {
+  return (gn_vw(d->io_dtype, d->C) == 8 && gn_ld16(d) && aligned16) ? 8 : 4;
+}
+int gn2_stat_vw(const ssbev_norm2_dims* d, bool aligned16) { return (gn_vw(d->io_dtype, d->C) == 8 && aligned16) ? 8 : 4; }
+
 GnGeom make_geom(const ssbev_norm_dims* d) {
   GnGeom g;
   g.B = d->B; g.C = d->C; g.G = d->G; g.S = d->S; g.eps = d->eps; g.relu = d->relu; g.pre = d->pre_act;
@@ -749,7 +764,7 @@ gn2_apply_fwd_kernel(const T* __restrict__ xa, const float* __restrict__ gamma_a
                      long totalv) {
   const int q = g.C / VW;
   const long stride = (long)gridDim.x * NT;
-  const bool fixed = stride % q == 0;
+  const bool fixed = apply_fixed(stride, q);
   long i = (long)blockIdx.x * NT + threadIdx.x;
   int c = (int)(i % q) * VW, bcur = -1;
   float ga[VW], ba[VW], gb[VW], bb[VW], mua[VW], rsa[VW], mub[VW], rsb[VW], d0[VW], d1[VW], d2[VW], d3[VW];
@@ -859,7 +874,7 @@ gn2_apply_bwd_kernel(const T* __restrict__ gy, const unsigned long long* __restr
                      T* __restrict__ gxa, T* __restrict__ gxb, Gn2Geom g, long totalv) {
   const int q = g.C / VW;
   const long stride = (long)gridDim.x * NT;
-  const bool fixed = stride % q == 0;
+  const bool fixed = apply_fixed(stride, q);
   long i = (long)blockIdx.x * NT + threadIdx.x;
   int c = (int)(i % q) * VW, bcur = -1;
   float ga[VW], gb[VW], mua[VW], rsa[VW], mub[VW], rsb[VW], c0a[VW], c1a[VW], c0b[VW], c1b[VW];
@@ -1013,9 +1028,7 @@ static int groupnorm_fwd_t(const T* x, const float* gamma, const float* beta, co
 }
 }  // extern "C++"
 
-// 16-byte lanes of bf16 tensors need 16-byte aligned rows
-static bool gn_rows16(const ssbev_norm_dims* d, const void* const* ptrs, int n) {
-  if ((d->ld_y != 0 && d->ld_y % 8 != 0) || (d->ld_gy != 0 && d->ld_gy % 8 != 0)) return false;
+static bool gn_ptrs16(const void* const* ptrs, int n) {
   for (int i = 0; i < n; ++i)
     if (ptrs[i] && reinterpret_cast<uintptr_t>(ptrs[i]) % 16 != 0) return false;
   return true;
@@ -1032,11 +1045,9 @@ static int groupnorm_fwd_impl(const float* x, const float* gamma, const float* b
     const bf16_t* x16 = reinterpret_cast<const bf16_t*>(x);
     const bf16_t* r16 = reinterpret_cast<const bf16_t*>(residual);
     bf16_t* y16 = reinterpret_cast<bf16_t*>(y);
-    if (gn_vw(1, d->C) == 8) {
-      const void* ps[1] = {x};
-      if (!gn_rows16(d, ps, 1)) return groupnorm_fwd_t<bf16_t, 4>(x16, gamma, beta, r16, y16, mean, rstd, mask, d, ws, stream, ext);
+    const void* ps[1] = {x};
+    if (gn_stat_vw(d, gn_ptrs16(ps, 1)) == 8)
       return groupnorm_fwd_t<bf16_t, 8>(x16, gamma, beta, r16, y16, mean, rstd, mask, d, ws, stream, ext);
-    }
     return groupnorm_fwd_t<bf16_t, 4>(x16, gamma, beta, r16, y16, mean, rstd, mask, d, ws, stream, ext);
   }
   return groupnorm_fwd_t<float, 4>(x, gamma, beta, residual, y, mean, rstd, mask, d, ws, stream, ext);
@@ -1121,13 +1132,11 @@ static int groupnorm_bwd_impl(const float* gy, const float* x, const float* y, c
   if (ws_bytes < ssbev_groupnorm_workspace(d)) return SSBEV_EWORKSPACE;
   if (d->io_dtype == 1) {
     typedef const bf16_t* cb;
-    if (gn_vw(1, d->C) == 8) {
-      const void* ps[3] = {gy, x, y};
-      if (gn_rows16(d, ps, 3))
-        return groupnorm_bwd_t<bf16_t, 8>(reinterpret_cast<cb>(gy), reinterpret_cast<cb>(x), reinterpret_cast<cb>(y), mask, gamma, mean,
+    const void* ps[3] = {gy, x, y};
+    if (gn_stat_vw(d, gn_ptrs16(ps, 3)) == 8)
+      return groupnorm_bwd_t<bf16_t, 8>(reinterpret_cast<cb>(gy), reinterpret_cast<cb>(x), reinterpret_cast<cb>(y), mask, gamma, mean,
                                         rstd, reinterpret_cast<bf16_t*>(gx), reinterpret_cast<bf16_t*>(gresidual), ggamma, gbeta, d, ws,
                                         stream, ext);
-    }
     return groupnorm_bwd_t<bf16_t, 4>(reinterpret_cast<cb>(gy), reinterpret_cast<cb>(x), reinterpret_cast<cb>(y), mask, gamma, mean, rstd,
                                       reinterpret_cast<bf16_t*>(gx), reinterpret_cast<bf16_t*>(gresidual), ggamma, gbeta, d, ws, stream, ext);
   }
@@ -1214,7 +1223,7 @@ static int groupnorm2_fwd_impl(const float* xa, const float* gamma_a, const floa
     typedef const bf16_t* cb;
     const bool al = reinterpret_cast<uintptr_t>(xa) % 16 == 0 && reinterpret_cast<uintptr_t>(xb) % 16 == 0 &&
                     reinterpret_cast<uintptr_t>(y) % 16 == 0;
-    if (gn_vw(1, d->C) == 8 && al) {
+    if (gn2_stat_vw(d, al) == 8) {
       return groupnorm2_fwd_t<bf16_t, 8>(reinterpret_cast<cb>(xa), gamma_a, beta_a, mean_a, rstd_a, reinterpret_cast<cb>(xb), gamma_b,
                                          beta_b, mean_b, rstd_b, reinterpret_cast<bf16_t*>(y), relu_mask, d, ws, stream, ext);
     }
@@ -1290,7 +1299,7 @@ static int groupnorm2_bwd_impl(const float* gy, const uint64_t* relu_mask, const
     bool al = true;
     for (const void* q : {(const void*)gy, (const void*)xa, (const void*)xb, (const void*)gxa, (const void*)gxb})
       al = al && reinterpret_cast<uintptr_t>(q) % 16 == 0;
-    if (gn_vw(1, d->C) == 8 && al) {
+    if (gn2_stat_vw(d, al) == 8) {
       return groupnorm2_bwd_t<bf16_t, 8>(reinterpret_cast<cb>(gy), relu_mask, reinterpret_cast<cb>(xa), gamma_a, mean_a, rstd_a,
                                          reinterpret_cast<cb>(xb), gamma_b, mean_b, rstd_b, reinterpret_cast<bf16_t*>(gxa),
                                          reinterpret_cast<bf16_t*>(gxb), ggamma_a, gbeta_a, ggamma_b, gbeta_b, d, ws, stream, ext);
@@ -1318,6 +1327,44 @@ int ssbev_groupnorm2_bwd_ext(const float* gy, const uint64_t* relu_mask, const f
                              ssbev_stream_t stream) {
   return groupnorm2_bwd_impl(gy, relu_mask, xa, gamma_a, mean_a, rstd_a, xb, gamma_b, mean_b, rstd_b, gxa, gxb, ggamma_a, gbeta_a,
                              ggamma_b, gbeta_b, d, ws, ws_bytes, stream, ext);
+}
+
+// Host-side plan query: every number below comes from the function the launchers and the *_workspace queries call themselves
+// (gn_stat_vw, make_geom, gn_slabs, make_geom2, apply_blocks, apply_fixed).
+int ssbev_groupnorm_plan_query(const ssbev_norm_dims* d, const ssbev_norm2_dims* d2, int aligned16, ssbev_groupnorm_plan* out) {
+  if (!out || (d != nullptr) == (d2 != nullptr)) return SSBEV_EINVAL;
+  ssbev_norm_dims side_b;
+  ssbev_groupnorm_plan p = {};
+  int C;
+  long totalv;
+  if (d) {
+    if (!gn_ok(d)) return SSBEV_EINVAL;
+    p.vw = gn_stat_vw(d, aligned16 != 0);
+    C = d->C;
+    totalv = (long)d->B * d->S * (d->C / 4);
+  } else {
+    if (!gn2_ok(d2)) return SSBEV_EINVAL;
+    p.vw = gn2_stat_vw(d2, aligned16 != 0);
+    C = d2->C;
+    totalv = (long)d2->B * d2->S * (d2->C / 4);
+    const Gn2Geom g2 = make_geom2(d2);
+    p.chunks2 = g2.chunks;
+    p.chunk_len2 = g2.chunk_len;
+    side_b = gn2_side(d2, 1);
+    const GnGeom gb = make_geom(&side_b);
+    p.chunks_b = gb.chunks;
+    p.chunk_len_b = gb.chunk_len;
+  }
+  const ssbev_norm_dims side_a = d ? *d : gn2_side(d2, 0);
+  const GnGeom g = make_geom(&side_a);
+  p.slab_q = g.slab_q;
+  p.slabs = (int)gn_slabs(g, p.vw);
+  p.chunks = g.chunks;
+  p.chunk_len = g.chunk_len;
+  p.blocks = apply_blocks(totalv, C / 4);
+  p.fixed = apply_fixed((long)p.blocks * NT, C / 4) ? 1 : 0;
+  *out = p;
+  return SSBEV_OK;
 }
 
 }  // extern "C"
