@@ -15,8 +15,15 @@
 //                                  outputs enumerated per PARITY CLASS (o mod stride) so that the valid taps are uniform
 //                                  over a tile: no wasted MFMAs on transposed convolutions.  Register tilings chosen per
 //                                  problem from measured sweeps (dispatch_gather); <1,5> is software pipelined.
+//   conv_igemm_kernel<...>         the same gathers with >= 64 output and a multiple of 32 input channels, LDS-staged.
 //   conv_tap_kernel                forward / data gradient of the <= 32-channel stride-1 3x3x3 layers: input rows in an
 //                                  LDS ring (global_load_lds), weights in registers, taps split over the waves.
+//   conv_taph_kernel               ... with F(2,3) along h inside the walk (even H).
+//   conv_tapdh_kernel              ... with F(2,3) along d and h (even D and H); wgrad_tapdh_kernel is its weight gradient.
+//   conv_tap2_kernel               k3 s2 p1 "down" gather, <= 32 -> 33..64 channels, on a row-pair ring.
+//   conv_tap2up_kernel             k3 s2 p1 "up" gather (fine grid = 2 x coarse), 33..64 -> <= 32 channels.
+//   conv_pw32_kernel               1x1x1 stride-1 layers with <= 32 channels on both sides, streaming.
+//   conv_thin_kernel               16..32 -> <= 4 channel heads as a VALU dot product over the LDS ring (wgrad_thin_kernel).
 //   wgrad_lds_kernel<...>          weight gradient of the 3x3(x3) layers (stride 1, stride 2, transposed): both operands
 //                                  staged through LDS, 9 accumulators per wave.
 //   wgrad_1x1_kernel, wgrad_cf_kernel, wgrad_kernel   weight gradients outside that family (1x1 streaming; dilated via
@@ -24,6 +31,8 @@
 //                                  partial tiles in a fixed order (deterministic, no float atomics).
 // The wide (>= 64 channel) stride-1 3x3(x3) layers normally do not come here at all: functional.conv3d / conv2d route them
 // through the Winograd path (winograd.hip).
+// Which kernel serves a call is decided in ONE place per direction, at the end of this file: select_conv_path (forward and data
+// gradient) and select_wgrad (weight gradient, with its workspace layout).  Every ssbev_conv_* entry point switches over those.
 #include "common.h"
 #include "conv_bf16.h"
 #include "conv_thin_mfma.h"
@@ -34,6 +43,7 @@
 #include <array>
 #include <map>
 #include <mutex>
+#include <type_traits>
 
 namespace {
 
@@ -690,6 +700,32 @@ bool conv_dims_ok(const ssbev_conv_dims* d) {
 
 int pad8(int c) { return (c + 7) & ~7; }
 int pad32(int c) { return (c + 31) & ~31; }
+size_t align256b(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// 3x3x3 taps, stride s on every axis, pad 1, no dilation: the shape of every ring-walk kernel and of its weight gradient
+bool is_k3_p1_d1(const ssbev_conv_dims* d, int s) {
+  return d->kd == 3 && d->kh == 3 && d->kw == 3 && d->sd == s && d->sh == s && d->sw == s &&
+         d->pd == 1 && d->ph == 1 && d->pw == 1 && d->dd == 1 && d->dh == 1 && d->dw == 1;
+}
+bool same_grid(const ssbev_conv_dims* d) { return d->Di == d->Do && d->Hi == d->Ho && d->Wi == d->Wo; }
+
+// The generic gather's view of a call (conv_gather_kernel / conv_igemm_kernel).  mode 0 (forward) gathers x into y; mode 1 (data
+// gradient) swaps the roles: source grid = forward output grid, K = Cout, N = Cin, and the gradient of a conv gathers like a
+// deconv and vice versa.
+ConvGeom make_gather_geom(const ssbev_conv_dims* d, int mode) {
+  const bool fwd = mode == 0;
+  ConvGeom g;
+  g.B = d->B; g.Cin = fwd ? d->Cin : d->Cout; g.Cout = fwd ? d->Cout : d->Cin; g.CinPad = pad8(g.Cin); g.CoutPad = pad32(g.Cout);
+  g.Di = fwd ? d->Di : d->Do; g.Hi = fwd ? d->Hi : d->Ho; g.Wi = fwd ? d->Wi : d->Wo;
+  g.Do = fwd ? d->Do : d->Di; g.Ho = fwd ? d->Ho : d->Hi; g.Wo = fwd ? d->Wo : d->Wi;
+  g.kd = d->kd; g.kh = d->kh; g.kw = d->kw; g.sd = d->sd; g.sh = d->sh; g.sw = d->sw;
+  g.pd = d->pd; g.ph = d->ph; g.pw = d->pw; g.dd = d->dd; g.dh = d->dh; g.dw = d->dw;
+  g.form = (d->transposed != 0) == fwd ? 1 : 0;
+  g.relu = fwd ? d->relu : 0; g.accumulate = d->accumulate;
+  g.hint = d->tile_hint >= 10 ? d->tile_hint : 0;       // hints below 10 select other kernel families
+  g.chunk_taps = 0; g.bf16 = d->precision == 1;
+  return g;
+}
 
 template <int MT, int NT, int QU>
 int launch_gather(const float* x, const float* wp, const float* bias, float* y, const ConvGeom& g, hipStream_t st) {
@@ -1097,9 +1133,8 @@ int launch_igemm(const float* x, const float* wp, const float* bias, float* y, c
   return SSBEV_EINVAL;
 }
 
+// register tiling of conv_gather_kernel for a problem (select_conv_path has sent the conv_igemm_kernel layers elsewhere)
 int dispatch_gather(const float* x, const float* wp, const float* bias, float* y, const ConvGeom& g, hipStream_t st) {
-  if (g.Cin % 4 != 0) return SSBEV_EINVAL;
-  if (conv_igemm_applicable(g)) return launch_igemm(x, wp, bias, y, g, st);
   if (g.hint) return launch_gather_cfg(g.hint / 100, (g.hint / 10) % 10, g.hint % 10, x, wp, bias, y, g, st);
   const long Mtot = (long)g.B * g.Do * g.Ho * g.Wo;
   // 48x160 feature maps (7680 pixels = 240 row tiles): <1,5> makes 240 x (Cout/160) waves -- 960 of the chip's 1024
@@ -1138,6 +1173,24 @@ int dispatch_gather(const float* x, const float* wp, const float* bias, float* y
 }
 
 struct WgradCfg { int MQ, MP, TH, TW; };
+
+// tile configuration of the tiled weight-gradient kernels (wgrad_cf_kernel, wgrad_kernel) for a problem
+WgradCfg wgrad_cfg(int Cp, int Cq, int kh, int kw) {
+  if (kh * kw == 1) return {2, 2, 1, 1};
+  if (Cp > 32 && Cq > 32) return {2, 2, 1, 3};
+  if (Cp <= 32 && Cq <= 32) return {1, 1, 3, 3};
+  return {1, 1, 1, 3};
+}
+
+// ... and its <MQ, MP, TH, TW> instantiation: f receives the four values as std::integral_constants
+template <int V> using Int = std::integral_constant<int, V>;
+template <typename F>
+void with_wgrad_cfg(const WgradCfg& c, F f) {
+  if (c.TH == 1 && c.TW == 1) f(Int<2>{}, Int<2>{}, Int<1>{}, Int<1>{});
+  else if (c.MQ == 2) f(Int<2>{}, Int<2>{}, Int<1>{}, Int<3>{});
+  else if (c.TH == 3) f(Int<1>{}, Int<1>{}, Int<3>{}, Int<3>{});
+  else f(Int<1>{}, Int<1>{}, Int<1>{}, Int<3>{});
+}
 
 // ---------------------------------------------------------------- weight gradient, channels-first path
 // For stride-1 "same" convolutions (the bulk of the FLOPs) the weight gradient is computed from two
@@ -1398,9 +1451,9 @@ wgrad_1x1_kernel(const float* __restrict__ P, const float* __restrict__ Q, float
 struct Wgrad1x1Plan { bool ok; int MQ, MP, chunk, nchunks; long N; int Cp, Cq; };
 
 Wgrad1x1Plan plan_wgrad_1x1(const ssbev_conv_dims* d) {
-  Wgrad1x1Plan p;
+  Wgrad1x1Plan p{};
   p.ok = d->kd == 1 && d->kh == 1 && d->kw == 1 && d->sd == 1 && d->sh == 1 && d->sw == 1 && d->pd == 0 && d->ph == 0 &&
-         d->pw == 0 && d->Di == d->Do && d->Hi == d->Ho && d->Wi == d->Wo;
+         d->pw == 0 && same_grid(d);
   if (!p.ok) return p;
   p.Cp = d->transposed ? d->Cin : d->Cout;
   p.Cq = d->transposed ? d->Cout : d->Cin;
@@ -1418,6 +1471,15 @@ Wgrad1x1Plan plan_wgrad_1x1(const ssbev_conv_dims* d) {
   p.chunk = (int)chunk;
   p.nchunks = (int)cdiv((p.N + chunk - 1) / chunk, 16);       // partial tiles = workgroups (16 waves folded in LDS)
   return p;
+}
+
+// the wgrad_1x1_kernel<MQ, MP> instantiation of a plan: f receives the two values as std::integral_constants
+template <typename F>
+void with_wgrad_1x1_tile(const Wgrad1x1Plan& p, F f) {
+  if (p.MQ == 2 && p.MP == 2) f(Int<2>{}, Int<2>{});
+  else if (p.MQ == 2) f(Int<2>{}, Int<1>{});
+  else if (p.MP == 2) f(Int<1>{}, Int<2>{});
+  else f(Int<1>{}, Int<1>{});
 }
 
 // Weight gradient of 3x3 / 3x3x3 convolutions (stride 1 "same", stride-2 k3 p1, and the k3 s2 p1 op1 transposed
@@ -1818,7 +1880,7 @@ WgradLdsPlan plan_wgrad_lds(const ssbev_conv_dims* d) {
 }
 
 WgradLdsPlan plan_wgrad_lds_uncached(const ssbev_conv_dims* d) {
-  WgradLdsPlan p;
+  WgradLdsPlan p{};
   p.ok = false;
   if (d->dd != 1 || d->dh != 1 || d->dw != 1 || d->kh != 3 || d->kw != 3 || d->ph != 1 || d->pw != 1) return p;
   if ((d->kd != 1 && d->kd != 3) || d->pd != d->kd / 2 || d->Cin % 4 != 0 || d->Cout % 4 != 0) return p;
@@ -3694,11 +3756,9 @@ wgrad_thin_kernel(const float* __restrict__ X, const float* __restrict__ GY, flo
 struct WgradThinPlan { bool ok; ConvTapGeom g; int nchunks; };
 
 WgradThinPlan plan_wgrad_thin(const ssbev_conv_dims* d) {
-  WgradThinPlan p;
+  WgradThinPlan p{};
   p.ok = false;
-  if (d->transposed || d->kd != 3 || d->kh != 3 || d->kw != 3 || d->sd != 1 || d->sh != 1 || d->sw != 1) return p;
-  if (d->pd != 1 || d->ph != 1 || d->pw != 1 || d->dd != 1 || d->dh != 1 || d->dw != 1) return p;
-  if (d->Di != d->Do || d->Hi != d->Ho || d->Wi != d->Wo || d->tile_hint == 7) return p;
+  if (d->transposed || !is_k3_p1_d1(d, 1) || !same_grid(d) || d->tile_hint == 7) return p;
   if (d->Cin > 32 || d->Cin < 16 || d->Cin % 4 != 0 || d->Cout > kThinNP) return p;
   ConvTapGeom& g = p.g;
   g.B = d->B; g.D = d->Do; g.H = d->Ho; g.W = d->Wo; g.K = d->Cin; g.N = d->Cout;
@@ -3853,44 +3913,53 @@ conv_thin_kernel(const float* __restrict__ X, const float* __restrict__ wt, cons
 }
 
 bool conv_thin_applicable(const ssbev_conv_dims* d, int mode) {
-  if (d->transposed || d->kd != 3 || d->kh != 3 || d->kw != 3 || d->sd != 1 || d->sh != 1 || d->sw != 1) return false;
-  if (d->pd != 1 || d->ph != 1 || d->pw != 1 || d->dd != 1 || d->dh != 1 || d->dw != 1) return false;
-  if (d->Di != d->Do || d->Hi != d->Ho || d->Wi != d->Wo || d->accumulate || d->tile_hint == 8) return false;
+  if (d->transposed || !is_k3_p1_d1(d, 1) || !same_grid(d) || d->accumulate || d->tile_hint == 8) return false;
   const int K = mode == 0 ? d->Cin : d->Cout, N = mode == 0 ? d->Cout : d->Cin;
   if (K > 32 || K < 16 || K % 4 != 0 || N > kThinNP) return false;
   return d->tile_hint == 9 || (long)d->B * d->Do * d->Ho * ((d->Wo + kTapWseg - 1) / kTapWseg) >= 1024L * 16;
 }
 
 // Chunk plans of the row-walking kernels: the geometry a launcher hands to its kernel, g.gpc (row groups per workgroup chunk)
-// included.  Each launcher below and ssbev_conv_chunk_groups (the host-side plan query) call the SAME plan_* function, so the
-// query cannot drift from the launch.  has_bias is the launcher's to fill in (it depends on a pointer, not on the dims).
-ConvTapGeom plan_conv_thin(const ssbev_conv_dims* d, int mode) {
+// included.  run_conv and ssbev_conv_chunk_groups (the host-side plan query) call the SAME plan_* function, so the query cannot
+// drift from the launch.  has_bias is launch_walk's to fill in (it depends on a pointer, not on the dims).
+// tap_geom_base: the fields every plan shares, for a walk over the forward output grid in 32-voxel segments (the stride-2 plans
+// replace grid and nseg).  conv_thin_kernel has no accumulating epilogue: conv_thin_applicable refuses such calls, so
+// d->accumulate is ConvTapGeom's default 0 there.
+ConvTapGeom tap_geom_base(const ssbev_conv_dims* d, int mode) {
   ConvTapGeom g;
   g.B = d->B; g.D = d->Do; g.H = d->Ho; g.W = d->Wo;
   g.K = mode == 0 ? d->Cin : d->Cout;
   g.N = mode == 0 ? d->Cout : d->Cin;
   g.nseg = (g.W + kTapWseg - 1) / kTapWseg;
-  g.NG = g.B * g.D * g.H;
   g.relu = mode == 0 ? d->relu : 0;
   g.has_bias = 0;
+  g.accumulate = d->accumulate;
+  return g;
+}
+
+// Launch of a row-walking kernel on its plan: one workgroup per (chunk of g.gpc row groups, w-segment).  Every ring here is past
+// the 64 KB a kernel gets without asking; the condition is conv_thin_kernel's, whose weight table decides on which side it falls.
+template <typename Kernel>
+int launch_walk(Kernel kernel, int threads, size_t lds_bytes, const float* x, const float* wp, const float* bias, float* y,
+                ConvTapGeom g, int mode, hipStream_t st) {
+  g.has_bias = (mode == 0 && bias) ? 1 : 0;
+  const long nranges = (g.NG + g.gpc - 1) / g.gpc;
+  if (lds_bytes > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
+    return SSBEV_ELAUNCH;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(nranges * g.nseg)), dim3(threads), lds_bytes, st, x, wp, bias, y, g);
+  return ssbev_launch_status();
+}
+
+constexpr size_t kThinLdsBytes = (size_t)(kTapRingF + 27 * kThinNP * 32) * sizeof(float);
+
+ConvTapGeom plan_conv_thin(const ssbev_conv_dims* d, int mode) {
+  ConvTapGeom g = tap_geom_base(d, mode);
+  g.NG = g.B * g.D * g.H;
   long nranges = std::max(1L, 1024L / g.nseg);
   if (nranges > g.NG) nranges = g.NG;
   g.gpc = (int)((g.NG + nranges - 1) / nranges);
   return g;
-}
-
-int launch_conv_thin(const float* x, const float* wt, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
-                     hipStream_t st) {
-  ConvTapGeom g = plan_conv_thin(d, mode);
-  g.has_bias = (mode == 0 && bias) ? 1 : 0;
-  const long nranges = (g.NG + g.gpc - 1) / g.gpc;
-  const size_t lds = (size_t)(kTapRingF + 27 * kThinNP * 32) * sizeof(float);
-  auto kern = conv_thin_kernel;
-  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)lds) != hipSuccess)
-    return SSBEV_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(nranges * g.nseg)), dim3(256), lds, st, x, wt, bias, y, g);
-  return ssbev_launch_status();
 }
 
 // Stride-2 "down" gather on conv_tap2_kernel: conv forward (mode 0, !transposed) or transposed-conv data gradient (mode 1,
@@ -3899,9 +3968,7 @@ int launch_conv_thin(const float* x, const float* wt, const float* bias, float* 
 bool conv_tap2_applicable(const ssbev_conv_dims* d, int mode) {
   static const bool enabled = !(ssbev_tune("SSBEV_TAP2") && atoi(ssbev_tune("SSBEV_TAP2")) == 0);          // A/B hook
   if (!enabled && d->tile_hint != 5) return false;
-  if (!((mode == 0 && !d->transposed) || (mode == 1 && d->transposed))) return false;
-  if (d->kd != 3 || d->kh != 3 || d->kw != 3 || d->sd != 2 || d->sh != 2 || d->sw != 2) return false;
-  if (d->pd != 1 || d->ph != 1 || d->pw != 1 || d->dd != 1 || d->dh != 1 || d->dw != 1) return false;
+  if (!((mode == 0 && !d->transposed) || (mode == 1 && d->transposed)) || !is_k3_p1_d1(d, 2)) return false;
   if (d->precision != 0 || d->tile_hint == 8 || (d->tile_hint != 0 && d->tile_hint != 5)) return false;
   const int K = mode == 0 ? d->Cin : d->Cout, N = mode == 0 ? d->Cout : d->Cin;
   if (K > 32 || K < 16 || K % 4 != 0 || N <= 32 || N > 64 || N % 4 != 0) return false;
@@ -3931,34 +3998,16 @@ int chunk_groups_by_rounds(int NG, int nseg, int H2, int cmax, double startup, d
 }
 
 ConvTapGeom plan_conv_tap2(const ssbev_conv_dims* d, int mode) {
-  ConvTapGeom g;
-  g.B = d->B;
+  ConvTapGeom g = tap_geom_base(d, mode);
   g.Ds = mode == 0 ? d->Di : d->Do; g.Hs = mode == 0 ? d->Hi : d->Ho; g.Ws = mode == 0 ? d->Wi : d->Wo;
   g.D = mode == 0 ? d->Do : d->Di; g.H = mode == 0 ? d->Ho : d->Hi; g.W = mode == 0 ? d->Wo : d->Wi;
-  g.K = mode == 0 ? d->Cin : d->Cout;
-  g.N = mode == 0 ? d->Cout : d->Cin;
   g.nseg = (g.W + 15) / 16;
   const int H2 = (g.H + 1) / 2;
   g.NG = g.B * g.D * H2;                     // output row pairs
-  g.relu = mode == 0 ? d->relu : 0;
-  g.has_bias = 0;
-  g.accumulate = d->accumulate;
   // one 512-thread workgroup per CU (150 KB of LDS): whole rounds of 256 workgroups, chunk start-up ~1 pair, plane crossing ~0.5
   g.gpc = chunk_groups_by_rounds(g.NG, g.nseg, H2, 96, 1.0, 0.5);
   if (const char* e = ssbev_tune("SSBEV_TAP2_GPC")) { const int v = atoi(e); if (v > 0) g.gpc = v; }   // tuning hook
   return g;
-}
-
-int launch_conv_tap2(const float* x, const float* wp, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
-                     hipStream_t st) {
-  ConvTapGeom g = plan_conv_tap2(d, mode);
-  g.has_bias = (mode == 0 && bias) ? 1 : 0;
-  const long nranges = (g.NG + g.gpc - 1) / g.gpc;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tap2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)kT2LdsBytes) != hipSuccess)
-    return SSBEV_ELAUNCH;
-  hipLaunchKernelGGL(conv_tap2_kernel, dim3((unsigned)(nranges * g.nseg)), dim3(512), kT2LdsBytes, st, x, wp, bias, y, g);
-  return ssbev_launch_status();
 }
 
 // Stride-2 "up" gather on conv_tap2up_kernel: transposed-conv forward (mode 0, transposed) or conv data gradient (mode 1,
@@ -3966,9 +4015,7 @@ int launch_conv_tap2(const float* x, const float* wp, const float* bias, float* 
 bool conv_tap2up_applicable(const ssbev_conv_dims* d, int mode) {
   static const bool enabled = !(ssbev_tune("SSBEV_TAP2UP") && atoi(ssbev_tune("SSBEV_TAP2UP")) == 0);      // A/B hook
   if (!enabled && d->tile_hint != 5) return false;
-  if (!((mode == 0 && d->transposed) || (mode == 1 && !d->transposed))) return false;
-  if (d->kd != 3 || d->kh != 3 || d->kw != 3 || d->sd != 2 || d->sh != 2 || d->sw != 2) return false;
-  if (d->pd != 1 || d->ph != 1 || d->pw != 1 || d->dd != 1 || d->dh != 1 || d->dw != 1) return false;
+  if (!((mode == 0 && d->transposed) || (mode == 1 && !d->transposed)) || !is_k3_p1_d1(d, 2)) return false;
   if (d->precision != 0 || d->tile_hint == 8 || (d->tile_hint != 0 && d->tile_hint != 5)) return false;
   const int K = mode == 0 ? d->Cin : d->Cout, N = mode == 0 ? d->Cout : d->Cin;
   if (K <= 32 || K > 64 || K % 4 != 0 || N > 32 || N < 16 || N % 8 != 0) return false;
@@ -3981,40 +4028,20 @@ bool conv_tap2up_applicable(const ssbev_conv_dims* d, int mode) {
 }
 
 ConvTapGeom plan_conv_tap2up(const ssbev_conv_dims* d, int mode) {
-  ConvTapGeom g;
-  g.B = d->B;
+  ConvTapGeom g = tap_geom_base(d, mode);
   g.Ds = mode == 0 ? d->Di : d->Do; g.Hs = mode == 0 ? d->Hi : d->Ho; g.Ws = mode == 0 ? d->Wi : d->Wo;
   g.D = 2 * g.Ds; g.H = 2 * g.Hs; g.W = 2 * g.Ws;
-  g.K = mode == 0 ? d->Cin : d->Cout;
-  g.N = mode == 0 ? d->Cout : d->Cin;
   g.nseg = (g.Ws + 15) / 16;
   const int H2 = (g.Hs + 1) / 2;
   g.NG = g.B * g.Ds * H2;                    // coarse row pairs
-  g.relu = mode == 0 ? d->relu : 0;
-  g.has_bias = 0;
-  g.accumulate = d->accumulate;
   g.gpc = chunk_groups_by_rounds(g.NG, g.nseg, H2, 96, 1.0, 0.5);          // as plan_conv_tap2
   if (const char* e = ssbev_tune("SSBEV_TAP2UP_GPC")) { const int v = atoi(e); if (v > 0) g.gpc = v; }   // tuning hook
   return g;
 }
 
-int launch_conv_tap2up(const float* x, const float* wp, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
-                       hipStream_t st) {
-  ConvTapGeom g = plan_conv_tap2up(d, mode);
-  g.has_bias = (mode == 0 && bias) ? 1 : 0;
-  const long nranges = (g.NG + g.gpc - 1) / g.gpc;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tap2up_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)kUpLdsBytes) != hipSuccess)
-    return SSBEV_ELAUNCH;
-  hipLaunchKernelGGL(conv_tap2up_kernel, dim3((unsigned)(nranges * g.nseg)), dim3(1024), kUpLdsBytes, st, x, wp, bias, y, g);
-  return ssbev_launch_status();
-}
-
 // tile_hint 8 forces the generic gather kernels (A/B timing), 9 forces this kernel on small problems (tests)
 bool conv_tap_applicable(const ssbev_conv_dims* d, int mode) {
-  if (d->transposed || d->kd != 3 || d->kh != 3 || d->kw != 3 || d->sd != 1 || d->sh != 1 || d->sw != 1) return false;
-  if (d->pd != 1 || d->ph != 1 || d->pw != 1 || d->dd != 1 || d->dh != 1 || d->dw != 1) return false;
-  if (d->Di != d->Do || d->Hi != d->Ho || d->Wi != d->Wo || d->tile_hint == 8) return false;
+  if (d->transposed || !is_k3_p1_d1(d, 1) || !same_grid(d) || d->tile_hint == 8) return false;
   if (d->Cin > 32 || d->Cout > 32) return false;
   const int K = mode == 0 ? d->Cin : d->Cout;
   if (K % 4 != 0) return false;
@@ -4035,8 +4062,7 @@ bool conv_pw32_applicable(const ssbev_conv_dims* d, int mode) {
   static const int off = ssbev_tune("SSBEV_PW32") ? atoi(ssbev_tune("SSBEV_PW32")) == 0 : 0;
   if (off || d->transposed || d->precision != 0 || d->tile_hint == 8) return false;
   if (d->kd != 1 || d->kh != 1 || d->kw != 1 || d->sd != 1 || d->sh != 1 || d->sw != 1) return false;
-  if (d->pd != 0 || d->ph != 0 || d->pw != 0) return false;
-  if (d->Di != d->Do || d->Hi != d->Ho || d->Wi != d->Wo) return false;
+  if (d->pd != 0 || d->ph != 0 || d->pw != 0 || !same_grid(d)) return false;
   if (d->Cin > 32 || d->Cout > 32 || d->Cin % 4 || d->Cout % 4 || d->Cin < 8 || d->Cout < 8) return false;
   (void)mode;
   return (long)d->B * d->Do * d->Ho * d->Wo >= 32768;
@@ -4068,15 +4094,8 @@ bool conv_tapdh_applicable(const ssbev_conv_dims* d, int mode) {
 }
 
 ConvTapGeom plan_conv_tapdh(const ssbev_conv_dims* d, int mode) {
-  ConvTapGeom g;
-  g.B = d->B; g.D = d->Do; g.H = d->Ho; g.W = d->Wo;
-  g.K = mode == 0 ? d->Cin : d->Cout;
-  g.N = mode == 0 ? d->Cout : d->Cin;
-  g.nseg = (g.W + kTapWseg - 1) / kTapWseg;
+  ConvTapGeom g = tap_geom_base(d, mode);
   g.NG = g.B * (g.D / 2) * (g.H / 2);        // 2 x 2 (plane, row) blocks
-  g.relu = mode == 0 ? d->relu : 0;
-  g.has_bias = 0;
-  g.accumulate = d->accumulate;
   // one 1024-thread workgroup per CU (149 KB of LDS); chunk length as in plan_conv_taph: whole rounds of 256 workgroups,
   // then the start-up of a chunk (weights + first four rows of four planes) and the restage at every plane-pair crossing
   g.gpc = chunk_groups_by_rounds(g.NG, g.nseg, g.H / 2, 96, 0.5, 0.3);
@@ -4087,18 +4106,13 @@ ConvTapGeom plan_conv_tapdh(const ssbev_conv_dims* d, int mode) {
 int launch_conv_tapdh(const float* x, const float* wp, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
                       hipStream_t st) {
   ConvTapGeom g = plan_conv_tapdh(d, mode);
-  g.has_bias = (mode == 0 && bias) ? 1 : 0;
-  const long nranges = (g.NG + g.gpc - 1) / g.gpc;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tapdh_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)kDhLdsBytes) != hipSuccess)
-    return SSBEV_ELAUNCH;
   static const int times = ssbev_tune("SSBEV_TAPDH_TIMES") ? atoi(ssbev_tune("SSBEV_TAPDH_TIMES")) : 0;
   if (times) {      // tuning hook: per-phase shader clocks of every wave (fresh stage / walk / publish + barrier / fold / tail barrier)
-    const size_t nwg = (size_t)(nranges * g.nseg), n = nwg * 16 * 8;
+    const size_t nwg = (size_t)((g.NG + g.gpc - 1) / g.gpc) * g.nseg, n = nwg * 16 * 8;
     unsigned long long* dev = nullptr;
     if (hipMalloc(&dev, n * 8) != hipSuccess) return SSBEV_ELAUNCH;
     g.dbg = dev;
-    hipLaunchKernelGGL(conv_tapdh_kernel, dim3((unsigned)nwg), dim3(1024), kDhLdsBytes, st, x, wp, bias, y, g);
+    const int rc = launch_walk(conv_tapdh_kernel, 1024, kDhLdsBytes, x, wp, bias, y, g, mode, st);
     std::vector<unsigned long long> h(n);
     hipStreamSynchronize(st);
     hipMemcpy(h.data(), dev, n * 8, hipMemcpyDeviceToHost);
@@ -4122,24 +4136,20 @@ int launch_conv_tapdh(const float* x, const float* wp, const float* bias, float*
             " | per chunk: life %.0f for %.1f blocks | kernel span %.0f ticks, %zu workgroups\n",
             ph[0] / blocks, ph[1] / blocks, ph[2] / blocks, ph[3] / blocks, ph[4] / blocks, life / (nwg * 16), blocks / (nwg * 16),
             (double)(t1 - t0), nwg);
-    return ssbev_launch_status();
+    return rc != SSBEV_OK ? rc : ssbev_launch_status();     // (after the synchronize: errors raised while the kernel ran)
   }
-  hipLaunchKernelGGL(conv_tapdh_kernel, dim3((unsigned)(nranges * g.nseg)), dim3(1024), kDhLdsBytes, st, x, wp, bias, y, g);
-  return ssbev_launch_status();
+  return launch_walk(conv_tapdh_kernel, 1024, kDhLdsBytes, x, wp, bias, y, g, mode, st);
 }
 
 // weight gradient of the conv_tapdh layers in the F(2,3) x F(2,3) domain (wgrad_tapdh_kernel).  tile_hint 9 forces it on
 // small problems (tests); 4 / 5 / 6 / 7 keep the older kernels (A/B timing)
-size_t align256b(size_t x);
 struct WgradDhPlan { bool ok; WgradDhGeom g; int nchunks; };
 WgradDhPlan plan_wgrad_dh(const ssbev_conv_dims* d) {
   static const int off = ssbev_tune("SSBEV_WGRAD_DH") ? atoi(ssbev_tune("SSBEV_WGRAD_DH")) == 0 : 0;
-  WgradDhPlan p;
+  WgradDhPlan p{};
   p.ok = false; p.nchunks = 0;
   if (off || d->transposed || d->precision != 0) return p;
-  if (d->kd != 3 || d->kh != 3 || d->kw != 3 || d->sd != 1 || d->sh != 1 || d->sw != 1) return p;
-  if (d->pd != 1 || d->ph != 1 || d->pw != 1 || d->dd != 1 || d->dh != 1 || d->dw != 1) return p;
-  if (d->Di != d->Do || d->Hi != d->Ho || d->Wi != d->Wo || d->Do % 2 || d->Ho % 2) return p;
+  if (!is_k3_p1_d1(d, 1) || !same_grid(d) || d->Do % 2 || d->Ho % 2) return p;
   if (d->Cin > 32 || d->Cout > 32 || d->Cin % 4 || d->Cout % 4 || d->Cin < 16 || d->Cout < 8) return p;
   if (d->tile_hint == 4 || d->tile_hint == 5 || d->tile_hint == 6 || d->tile_hint == 7 || d->tile_hint == 8) return p;
   const int nseg = (d->Wo + kTapWseg - 1) / kTapWseg;
@@ -4158,14 +4168,8 @@ WgradDhPlan plan_wgrad_dh(const ssbev_conv_dims* d) {
   return p;
 }
 
-size_t wgrad_dh_workspace(const WgradDhPlan& p) {
-  const size_t tile = (size_t)48 * p.g.Cq * p.g.Cp * sizeof(float);
-  return align256b((size_t)p.nchunks * tile) + align256b(tile);
-}
-
-int run_wgrad_dh(const float* x, const float* gy, float* gw, const WgradDhPlan& p, void* ws, hipStream_t st) {
-  float* partial = static_cast<float*>(ws);
-  float* gU = reinterpret_cast<float*>(static_cast<char*>(ws) + align256b((size_t)p.nchunks * 48 * p.g.Cq * p.g.Cp * sizeof(float)));
+// partial: the chunk partials [nchunks][48][Cq][Cp]; gU: their sum, one [48][Cq][Cp] tile (both sections of the caller's workspace)
+int run_wgrad_dh(const float* x, const float* gy, float* gw, const WgradDhPlan& p, float* partial, float* gU, hipStream_t st) {
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_tapdh_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)kWdLdsBytes) != hipSuccess)
     return SSBEV_ELAUNCH;
@@ -4177,15 +4181,8 @@ int run_wgrad_dh(const float* x, const float* gy, float* gw, const WgradDhPlan& 
 }
 
 ConvTapGeom plan_conv_taph(const ssbev_conv_dims* d, int mode) {
-  ConvTapGeom g;
-  g.B = d->B; g.D = d->Do; g.H = d->Ho; g.W = d->Wo;
-  g.K = mode == 0 ? d->Cin : d->Cout;
-  g.N = mode == 0 ? d->Cout : d->Cin;
-  g.nseg = (g.W + kTapWseg - 1) / kTapWseg;
+  ConvTapGeom g = tap_geom_base(d, mode);
   g.NG = g.B * g.D * (g.H / 2);              // row pairs
-  g.relu = mode == 0 ? d->relu : 0;
-  g.has_bias = 0;
-  g.accumulate = d->accumulate;
   // One 512-thread workgroup per CU (141 KB of LDS).  Chunk length (row pairs per workgroup) by a small cost model fitted on
   // the 192 x 48 x 160 layer (tools/taph_gpc_probe.py): whole rounds of 256 workgroups matter most (the last round's idle
   // CUs: 12 pairs -> 7.5 rounds 0.580 ms, 18 pairs -> 5.0 rounds 0.537 ms), then the start-up of a chunk (weights + first
@@ -4198,29 +4195,9 @@ ConvTapGeom plan_conv_taph(const ssbev_conv_dims* d, int mode) {
   return g;
 }
 
-int launch_conv_taph(const float* x, const float* wp, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
-                     hipStream_t st) {
-  ConvTapGeom g = plan_conv_taph(d, mode);
-  g.has_bias = (mode == 0 && bias) ? 1 : 0;
-  const long nranges = (g.NG + g.gpc - 1) / g.gpc;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_taph_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)kTwLdsBytes) != hipSuccess)
-    return SSBEV_ELAUNCH;
-  hipLaunchKernelGGL(conv_taph_kernel, dim3((unsigned)(nranges * g.nseg)), dim3(512), kTwLdsBytes, st, x, wp,
-                     bias, y, g);
-  return ssbev_launch_status();
-}
-
 ConvTapGeom plan_conv_tap(const ssbev_conv_dims* d, int mode) {
-  ConvTapGeom g;
-  g.B = d->B; g.D = d->Do; g.H = d->Ho; g.W = d->Wo;
-  g.K = mode == 0 ? d->Cin : d->Cout;
-  g.N = mode == 0 ? d->Cout : d->Cin;
-  g.nseg = (g.W + kTapWseg - 1) / kTapWseg;
+  ConvTapGeom g = tap_geom_base(d, mode);
   g.NG = g.B * g.D * g.H;
-  g.relu = mode == 0 ? d->relu : 0;
-  g.has_bias = 0;
-  g.accumulate = d->accumulate;
   // two workgroups per CU; whole rounds of 512 workgroups, >= 16 rows each
   long nranges = 512 / g.nseg;
   for (long rounds = 8; rounds >= 1; --rounds) {
@@ -4232,22 +4209,8 @@ ConvTapGeom plan_conv_tap(const ssbev_conv_dims* d, int mode) {
   return g;
 }
 
-int launch_conv_tap(const float* x, const float* wp, const float* bias, float* y, const ssbev_conv_dims* d, int mode,
-                    hipStream_t st) {
-  ConvTapGeom g = plan_conv_tap(d, mode);
-  g.has_bias = (mode == 0 && bias) ? 1 : 0;
-  const long nranges = (g.NG + g.gpc - 1) / g.gpc;
-  auto kern = d->precision == 1 ? conv_tap_kernel<true> : conv_tap_kernel<false>;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)kTapLdsBytes) != hipSuccess)
-    return SSBEV_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(nranges * g.nseg)), dim3(256), kTapLdsBytes, st, x, wp, bias, y, g);
-  return ssbev_launch_status();
-}
-
 bool wgrad_cf_applicable(const ssbev_conv_dims* d) {
-  if (d->transposed || d->sd != 1 || d->sh != 1 || d->sw != 1) return false;
-  if (d->Di != d->Do || d->Hi != d->Ho || d->Wi != d->Wo) return false;
+  if (d->transposed || d->sd != 1 || d->sh != 1 || d->sw != 1 || !same_grid(d)) return false;
   if (d->Wo % 4 != 0 || ((long)d->B * d->Do * d->Ho * d->Wo) % 8 != 0) return false;
   if (2 * d->pd != d->dd * (d->kd - 1) || 2 * d->ph != d->dh * (d->kh - 1) || 2 * d->pw != d->dw * (d->kw - 1)) return false;
   return true;
@@ -4259,12 +4222,7 @@ WgradCfGeom make_wgrad_cf_geom(const ssbev_conv_dims* d, WgradCfg* cfg_out) {
   g.kd = d->kd; g.kh = d->kh; g.kw = d->kw; g.dd = d->dd; g.dh = d->dh; g.dw = d->dw;
   g.Dp = d->Di + 2 * d->pd; g.Hp = d->Hi + 2 * d->ph;
   g.Wp = ((d->Wi + 2 * d->pw + 3) & ~3) + 4;          // +4: slack for the last row's unaligned float4
-  WgradCfg c;
-  if (d->kh * d->kw == 1) c = {2, 2, 1, 1};
-  else if (g.Cp > 32 && g.Cq > 32) c = {2, 2, 1, 3};
-  else if (g.Cp <= 32 && g.Cq <= 32) c = {1, 1, 3, 3};
-  else c = {1, 1, 1, 3};
-  *cfg_out = c;
+  const WgradCfg c = *cfg_out = wgrad_cfg(g.Cp, g.Cq, g.kh, g.kw);
   const long N = (long)g.B * g.D * g.H * g.W;
   const long tiles = (long)((g.Cp + 32 * c.MP - 1) / (32 * c.MP)) * ((g.Cq + 32 * c.MQ - 1) / (32 * c.MQ)) * g.kd *
                      ((g.kh + c.TH - 1) / c.TH) * ((g.kw + c.TW - 1) / c.TW);
@@ -4287,21 +4245,11 @@ WgradCfGeom make_wgrad_cf_geom(const ssbev_conv_dims* d, WgradCfg* cfg_out) {
   return g;
 }
 
-size_t align256b(size_t x) { return (x + 255) & ~(size_t)255; }
-
 template <int MQ, int MP, int TH, int TW>
 void launch_wgrad_cf(const float* Pt, const float* Qp, float* ws, const WgradCfGeom& g, hipStream_t st) {
   const int ytiles = ((g.Cq + 32 * MQ - 1) / (32 * MQ)) * ((g.Cp + 32 * MP - 1) / (32 * MP));
   dim3 grid(cdiv(g.nchunks, 4), ytiles, g.kd * ((g.kh + TH - 1) / TH) * ((g.kw + TW - 1) / TW));
   hipLaunchKernelGGL((wgrad_cf_kernel<MQ, MP, TH, TW>), grid, dim3(256), 0, st, Pt, Qp, ws, g);
-}
-
-// tile configuration of the weight-gradient kernel for a problem
-WgradCfg wgrad_cfg(int Cp, int Cq, int kh, int kw) {
-  if (kh * kw == 1) return {2, 2, 1, 1};
-  if (Cp > 32 && Cq > 32) return {2, 2, 1, 3};
-  if (Cp <= 32 && Cq <= 32) return {1, 1, 3, 3};
-  return {1, 1, 1, 3};
 }
 
 WgradGeom make_wgrad_geom(const ssbev_conv_dims* d) {
@@ -4338,6 +4286,123 @@ void launch_wgrad(const float* P, const float* Qt, float* ws, const WgradGeom& g
   hipLaunchKernelGGL((wgrad_kernel<MQ, MP, TH, TW>), grid, dim3(256), 0, st, P, Qt, ws, g);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Dispatch.  select_conv_path is THE order in which the kernels above are offered a forward (mode 0) or data-gradient (mode 1)
+// call; ssbev_conv_fwd / ssbev_conv_bwd_data (run_conv), ssbev_conv_pack_weight, ssbev_conv_kernel_class and
+// ssbev_conv_chunk_groups all switch over its answer, so a weight is packed for the kernel that will read it and the queries
+// describe the launch.  A new kernel family is one enumerator, one line here and one case in each switch.
+enum class ConvPath { ThinIn, Thin, Tap2, Tap2Up, Pw32, TapDh, TapH, Tap, Igemm, Gather, Invalid };
+
+ConvPath select_conv_path(const ssbev_conv_dims* d, int mode) {
+  if (ssbev_thin::thinin_applicable(d, mode)) return ConvPath::ThinIn;
+  if (mode == 0 && d->Cin % 4 != 0) return ConvPath::Invalid;   // float4 channel loads: caller pads K channels to 4
+  if (conv_thin_applicable(d, mode)) return ConvPath::Thin;
+  if (conv_tap2_applicable(d, mode)) return ConvPath::Tap2;
+  if (conv_tap2up_applicable(d, mode)) return ConvPath::Tap2Up;
+  if (conv_pw32_applicable(d, mode)) return ConvPath::Pw32;
+  if (conv_tapdh_applicable(d, mode)) return ConvPath::TapDh;
+  if (conv_taph_applicable(d, mode)) return ConvPath::TapH;
+  if (conv_tap_applicable(d, mode)) return ConvPath::Tap;
+  const ConvGeom g = make_gather_geom(d, mode);
+  if (g.Cin % 4 != 0) return ConvPath::Invalid;                 // (the data gradient's K role is Cout; the kernels above refuse it themselves)
+  return conv_igemm_applicable(g) ? ConvPath::Igemm : ConvPath::Gather;
+}
+
+// mode 0: src = x, dst = y; mode 1: src = gy, dst = gx, no bias
+int run_conv(const float* src, const float* wp, const float* bias, float* dst, const ssbev_conv_dims* d, int mode, hipStream_t st) {
+  switch (select_conv_path(d, mode)) {
+    case ConvPath::ThinIn: return ssbev_thin::thinin_launch(src, wp, bias, dst, d, mode, st);
+    case ConvPath::Thin: return launch_walk(conv_thin_kernel, 256, kThinLdsBytes, src, wp, bias, dst, plan_conv_thin(d, mode), mode, st);
+    case ConvPath::Tap2: return launch_walk(conv_tap2_kernel, 512, kT2LdsBytes, src, wp, bias, dst, plan_conv_tap2(d, mode), mode, st);
+    case ConvPath::Tap2Up: return launch_walk(conv_tap2up_kernel, 1024, kUpLdsBytes, src, wp, bias, dst, plan_conv_tap2up(d, mode), mode, st);
+    case ConvPath::Pw32: return launch_conv_pw32(src, wp, bias, dst, d, mode, st);
+    case ConvPath::TapDh: return launch_conv_tapdh(src, wp, bias, dst, d, mode, st);
+    case ConvPath::TapH: return launch_walk(conv_taph_kernel, 512, kTwLdsBytes, src, wp, bias, dst, plan_conv_taph(d, mode), mode, st);
+    case ConvPath::Tap:
+      return launch_walk(d->precision == 1 ? conv_tap_kernel<true> : conv_tap_kernel<false>, 256, kTapLdsBytes, src, wp, bias, dst,
+                         plan_conv_tap(d, mode), mode, st);
+    case ConvPath::Igemm: return launch_igemm(src, wp, bias, dst, make_gather_geom(d, mode), st);
+    case ConvPath::Gather: return dispatch_gather(src, wp, bias, dst, make_gather_geom(d, mode), st);
+    case ConvPath::Invalid: break;
+  }
+  return SSBEV_EINVAL;
+}
+
+// public class number of a path (include/ssbev.h)
+int conv_path_class(ConvPath p) {
+  switch (p) {
+    case ConvPath::ThinIn: return 4;
+    case ConvPath::Thin: return 3;
+    case ConvPath::Tap2: return 7;              // stride-2 "down" gather on conv_tap2_kernel
+    case ConvPath::Tap2Up: return 8;            // stride-2 "up" gather on conv_tap2up_kernel
+    case ConvPath::Pw32: return 10;             // 1x1x1, <= 32 channels: streaming kernel
+    case ConvPath::TapDh: return 9;             // F(2,3) along d and h inside the tap walk
+    case ConvPath::TapH: return 2;
+    case ConvPath::Tap: return 1;
+    case ConvPath::Igemm: return 11;            // conv_igemm_kernel
+    default: return 0;                          // conv_gather_kernel; Invalid: the class query refuses nothing the launchers' K % 4 rule does
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// select_wgrad is the same for the weight gradient: the kind, its plan, and the layout of the caller's workspace (the partial
+// tiles always start it).  ssbev_conv_bwd_weight_workspace answers ws_bytes, ssbev_conv_bwd_weight carves the same offsets up.
+// tile_hint 7 forces the channel-major / direct kernels past the 1x1 and LDS ones (tests / A-B timing).
+enum class WgradKind { Bf16Storage, ThinSide, Thin, Pointwise, Dh, Lds, ChannelsFirst, Direct };
+
+struct WgradPlan {
+  WgradKind kind;
+  size_t ws_bytes = 0;
+  size_t gu_off = 0;                            // Dh: the summed [48][Cq][Cp] tile
+  size_t pt_off = 0, qp_off = 0, qp_bytes = 0;  // ChannelsFirst: channel-major gy, zero-padded channel-major x (qp_bytes to clear)
+  WgradThinPlan thin;
+  Wgrad1x1Plan p1;
+  WgradDhPlan dh;
+  WgradLdsPlan lds;
+  WgradCfGeom cf;
+  WgradGeom direct;
+  WgradCfg cfg;                                 // ChannelsFirst, Direct
+};
+
+WgradPlan select_wgrad(const ssbev_conv_dims* d) {
+  WgradPlan p{};
+  const size_t tile = (size_t)d->Cin * d->Cout * sizeof(float);          // one tap's [Cq][Cp] partial tile
+  const size_t taps = (size_t)d->kd * d->kh * d->kw;
+  if (ssbev_bf16::storage_mode(d)) {
+    p.kind = WgradKind::Bf16Storage;
+    p.ws_bytes = ssbev_bf16::wgrad_workspace(d);
+  } else if (ssbev_thin::wgrad_applicable(d)) {
+    p.kind = WgradKind::ThinSide;
+    p.ws_bytes = ssbev_thin::wgrad_workspace(d);
+  } else if ((p.thin = plan_wgrad_thin(d)).ok) {
+    p.kind = WgradKind::Thin;
+    p.ws_bytes = align256b((size_t)p.thin.nchunks * 27 * tile);
+  } else if ((p.p1 = plan_wgrad_1x1(d)).ok && d->tile_hint != 7) {
+    p.kind = WgradKind::Pointwise;
+    p.ws_bytes = align256b(p.p1.nchunks * tile);
+  } else if ((p.dh = plan_wgrad_dh(d)).ok) {
+    p.kind = WgradKind::Dh;
+    p.gu_off = align256b((size_t)p.dh.nchunks * 48 * tile);
+    p.ws_bytes = p.gu_off + align256b(48 * tile);
+  } else if ((p.lds = plan_wgrad_lds(d)).ok && d->tile_hint != 7) {
+    p.kind = WgradKind::Lds;
+    p.ws_bytes = align256b((size_t)p.lds.nchunks * p.lds.ksplit * d->kd * 9 * tile);
+  } else if (wgrad_cf_applicable(d)) {
+    p.kind = WgradKind::ChannelsFirst;
+    const WgradCfGeom& g = p.cf = make_wgrad_cf_geom(d, &p.cfg);
+    p.pt_off = align256b(g.nchunks * taps * tile);
+    p.qp_off = p.pt_off + align256b((size_t)g.Cp * g.B * g.D * g.H * g.W * sizeof(float));
+    p.qp_bytes = ((size_t)g.Cq * g.B * g.Dp * g.Hp * g.Wp + 16) * sizeof(float);
+    p.ws_bytes = p.qp_off + align256b(p.qp_bytes);
+  } else {
+    p.kind = WgradKind::Direct;
+    p.direct = make_wgrad_geom(d);
+    p.cfg = wgrad_cfg(p.direct.Cp, p.direct.Cq, p.direct.kh, p.direct.kw);
+    p.ws_bytes = p.direct.nchunks * taps * tile;
+  }
+  return p;
+}
+
 }  // namespace
 
 namespace ssbev_detail {
@@ -4353,39 +4418,21 @@ int ssbev_conv_kernel_class(const ssbev_conv_dims* d, int mode) {
   if (!conv_dims_ok(d) || mode < 0 || mode > 2) return SSBEV_EINVAL;
   if (ssbev_bf16::storage_mode(d)) return ssbev_bf16::dims_ok(d, mode) ? ssbev_bf16::kernel_class(d, mode) : SSBEV_EINVAL;
   if (mode == 2) return ssbev_thin::wgrad_applicable(d) ? 6 : 0;      // weight gradient: 6 = wgrad_thinside_kernel (unpadded thin side)
-  if (ssbev_thin::thinin_applicable(d, mode)) return 4;
-  if (ssbev_thin::thinout_applicable(d, mode)) return 5;     // ssbev_conv_thin_* (caller-owned workspace); ssbev_conv_fwd falls back to class 3 / 0
-  if (conv_thin_applicable(d, mode)) return 3;
-  if (conv_tap2_applicable(d, mode)) return 7;                // stride-2 "down" gather on conv_tap2_kernel
-  if (conv_tap2up_applicable(d, mode)) return 8;              // stride-2 "up" gather on conv_tap2up_kernel
-  if (conv_pw32_applicable(d, mode)) return 10;               // 1x1x1, <= 32 channels: streaming kernel
-  if (conv_tapdh_applicable(d, mode)) return 9;               // F(2,3) along d and h inside the tap walk
-  if (conv_taph_applicable(d, mode)) return 2;
-  if (conv_tap_applicable(d, mode)) return 1;
-  {                                                           // the generic gather: conv_igemm_kernel (11) or conv_gather_kernel (0)
-    ConvGeom g;
-    const bool fwd = mode == 0;
-    g.B = d->B; g.Cin = fwd ? d->Cin : d->Cout; g.Cout = fwd ? d->Cout : d->Cin; g.CinPad = pad8(g.Cin); g.CoutPad = pad32(g.Cout);
-    g.Di = fwd ? d->Di : d->Do; g.Hi = fwd ? d->Hi : d->Ho; g.Wi = fwd ? d->Wi : d->Wo;
-    g.Do = fwd ? d->Do : d->Di; g.Ho = fwd ? d->Ho : d->Hi; g.Wo = fwd ? d->Wo : d->Wi;
-    g.kd = d->kd; g.kh = d->kh; g.kw = d->kw; g.sd = d->sd; g.sh = d->sh; g.sw = d->sw;
-    g.pd = d->pd; g.ph = d->ph; g.pw = d->pw; g.dd = d->dd; g.dh = d->dh; g.dw = d->dw;
-    g.form = (d->transposed != 0) == fwd ? 1 : 0; g.relu = 0; g.accumulate = 0;
-    g.hint = d->tile_hint >= 10 ? d->tile_hint : 0; g.chunk_taps = 0; g.bf16 = d->precision == 1;
-    if (g.Cin % 4 == 0 && conv_igemm_applicable(g)) return 11;
-  }
-  return 0;
+  const ConvPath path = select_conv_path(d, mode);
+  // Class 5 (ssbev_conv_thin_*: two-pass kernels with a caller-owned workspace) exists as a class only: the caller runs those
+  // entry points itself.  It ranks right after thin-in; ssbev_conv_fwd / ssbev_conv_bwd_data / ssbev_conv_pack_weight do not know
+  // it and serve such dims with whatever select_conv_path says (class 3 / 0).  This is the one place that asymmetry lives.
+  if (path != ConvPath::ThinIn && ssbev_thin::thinout_applicable(d, mode)) return 5;
+  return conv_path_class(path);
 }
 
 int ssbev_conv_chunk_groups(const ssbev_conv_dims* d, int mode) {
   if (!conv_dims_ok(d) || mode < 0 || mode > 2) return 0;
-  if (mode == 2) {                                            // the order of ssbev_conv_bwd_weight
-    if (ssbev_bf16::storage_mode(d) || ssbev_thin::wgrad_applicable(d) || plan_wgrad_thin(d).ok) return 0;
-    if (plan_wgrad_1x1(d).ok && d->tile_hint != 7) return 0;
-    const WgradDhPlan hp = plan_wgrad_dh(d);
-    return hp.ok ? hp.g.gpc : 0;
+  if (mode == 2) {
+    const WgradPlan p = select_wgrad(d);
+    return p.kind == WgradKind::Dh ? p.dh.g.gpc : 0;
   }
-  switch (ssbev_conv_kernel_class(d, mode)) {
+  switch (ssbev_conv_kernel_class(d, mode)) {                 // (the class, not the path: a class-5 call is no walk of these kernels)
     case 1: return plan_conv_tap(d, mode).gpc;
     case 2: return plan_conv_taph(d, mode).gpc;
     case 3: return plan_conv_thin(d, mode).gpc;
@@ -4411,54 +4458,46 @@ size_t ssbev_conv_packed_weight_elems(const ssbev_conv_dims* d) {
 int ssbev_conv_pack_weight(const float* w_src, float* w_packed, const ssbev_conv_dims* d, int mode,
                            ssbev_stream_t stream) {
   if (!conv_dims_ok(d) || !w_src || !w_packed || (mode != 0 && mode != 1)) return SSBEV_EINVAL;
-  if (ssbev_bf16::storage_mode(d)) return ssbev_bf16::pack(w_src, w_packed, d, mode, as_stream(stream));
-  if (ssbev_thin::thinin_applicable(d, mode)) return ssbev_thin::thinin_pack(w_src, w_packed, d, mode, as_stream(stream));
-  if (conv_thin_applicable(d, mode)) {       // <= 4 output channels: LDS-resident [tap][n][k] table (conv_thin_kernel)
-    hipLaunchKernelGGL(pack_thin_kernel, dim3(cdiv(27 * kThinNP * 32, 256)), dim3(256), 0, as_stream(stream), w_src,
-                       w_packed, d->Cout, d->Cin, mode);
-    return ssbev_launch_status();
-  }
-  if (conv_tap2_applicable(d, mode)) {       // stride-2 "down" gather: [N][K][27] in both roles, see pack_tap2_kernel
-    const int K = mode == 0 ? d->Cin : d->Cout, N = mode == 0 ? d->Cout : d->Cin;
-    hipLaunchKernelGGL(pack_tap2_kernel, dim3(cdiv(kT2PackedElems, 256)), dim3(256), 0, as_stream(stream), w_src, w_packed, N, K);
-    return ssbev_launch_status();
-  }
-  if (conv_tap2up_applicable(d, mode)) {     // stride-2 "up" gather: [K][N][27] in both roles, see pack_tap2up_kernel
-    const int K = mode == 0 ? d->Cin : d->Cout, N = mode == 0 ? d->Cout : d->Cin;
-    hipLaunchKernelGGL(pack_tap2up_kernel, dim3(cdiv(kUpPackedElems, 256)), dim3(256), 0, as_stream(stream), w_src, w_packed, N, K);
-    return ssbev_launch_status();
-  }
-  if (conv_pw32_applicable(d, mode)) {
-    hipLaunchKernelGGL(pack_pw32_kernel, dim3(cdiv(kPwPackedElems, 256)), dim3(256), 0, as_stream(stream), w_src, w_packed,
-                       d->Cout, d->Cin, mode);
-    return ssbev_launch_status();
-  }
-  if (conv_tapdh_applicable(d, mode)) {      // Winograd along d and h: U = G w G^T per kw
-    hipLaunchKernelGGL(pack_tapdh_kernel, dim3(cdiv(kDhPackedElems, 256)), dim3(256), 0, as_stream(stream), w_src, w_packed,
-                       d->Cout, d->Cin, mode);
-    return ssbev_launch_status();
-  }
-  if (conv_taph_applicable(d, mode)) {       // Winograd-along-h variant of the tap kernel: U = G w per (kd, kw)
-    hipLaunchKernelGGL(pack_taph_kernel, dim3(cdiv(kTwPackedElems, 256)), dim3(256), 0, as_stream(stream), w_src, w_packed,
-                       d->Cout, d->Cin, mode);
-    return ssbev_launch_status();
-  }
-  if (conv_tap_applicable(d, mode)) {        // register-resident tap-split layout (see conv_tap_kernel)
-    hipLaunchKernelGGL(pack_tap_kernel, dim3(cdiv(kTapPackedElems, 256)), dim3(256), 0, as_stream(stream), w_src, w_packed,
-                       d->Cout, d->Cin, mode);
-    return ssbev_launch_status();
-  }
-  const int taps = d->kd * d->kh * d->kw;
+  hipStream_t st = as_stream(stream);
+  if (ssbev_bf16::storage_mode(d)) return ssbev_bf16::pack(w_src, w_packed, d, mode, st);
   // forward: K = Cin, N = Cout; data gradient: K = Cout, N = Cin
   const int K = mode == 0 ? d->Cin : d->Cout, N = mode == 0 ? d->Cout : d->Cin;
-  // torch layout: conv [Cout,Cin,k], deconv [Cin,Cout,k]
-  //   fwd conv  : K=A1 (layout 0)   fwd deconv: K=A0 (layout 1)
-  //   bwd conv  : K=A0 (layout 1)   bwd deconv: K=A1 (layout 0)
-  const int layout = (mode == 0) == (d->transposed == 0) ? 0 : 1;
-  const int KPad = pad8(K), NPad = pad32(N);
-  const long total = (long)taps * KPad * NPad;
-  hipLaunchKernelGGL(pack_weight_kernel, dim3(cdiv(total, 256)), dim3(256), 0, as_stream(stream), w_src, w_packed, K,
-                     N, KPad, NPad, taps, layout, total);
+  const dim3 block(256);
+  switch (select_conv_path(d, mode)) {
+    case ConvPath::ThinIn: return ssbev_thin::thinin_pack(w_src, w_packed, d, mode, st);
+    case ConvPath::Thin:       // <= 4 output channels: LDS-resident [tap][n][k] table (conv_thin_kernel)
+      hipLaunchKernelGGL(pack_thin_kernel, dim3(cdiv(27 * kThinNP * 32, 256)), block, 0, st, w_src, w_packed, d->Cout, d->Cin, mode);
+      break;
+    case ConvPath::Tap2:       // stride-2 "down" gather: [N][K][27] in both roles, see pack_tap2_kernel
+      hipLaunchKernelGGL(pack_tap2_kernel, dim3(cdiv(kT2PackedElems, 256)), block, 0, st, w_src, w_packed, N, K);
+      break;
+    case ConvPath::Tap2Up:     // stride-2 "up" gather: [K][N][27] in both roles, see pack_tap2up_kernel
+      hipLaunchKernelGGL(pack_tap2up_kernel, dim3(cdiv(kUpPackedElems, 256)), block, 0, st, w_src, w_packed, N, K);
+      break;
+    case ConvPath::Pw32:
+      hipLaunchKernelGGL(pack_pw32_kernel, dim3(cdiv(kPwPackedElems, 256)), block, 0, st, w_src, w_packed, d->Cout, d->Cin, mode);
+      break;
+    case ConvPath::TapDh:      // Winograd along d and h: U = G w G^T per kw
+      hipLaunchKernelGGL(pack_tapdh_kernel, dim3(cdiv(kDhPackedElems, 256)), block, 0, st, w_src, w_packed, d->Cout, d->Cin, mode);
+      break;
+    case ConvPath::TapH:       // Winograd-along-h variant of the tap kernel: U = G w per (kd, kw)
+      hipLaunchKernelGGL(pack_taph_kernel, dim3(cdiv(kTwPackedElems, 256)), block, 0, st, w_src, w_packed, d->Cout, d->Cin, mode);
+      break;
+    case ConvPath::Tap:        // register-resident tap-split layout (see conv_tap_kernel)
+      hipLaunchKernelGGL(pack_tap_kernel, dim3(cdiv(kTapPackedElems, 256)), block, 0, st, w_src, w_packed, d->Cout, d->Cin, mode);
+      break;
+    case ConvPath::Igemm: case ConvPath::Gather: case ConvPath::Invalid: {     // (Invalid: the launch will refuse; packing never did)
+      const int taps = d->kd * d->kh * d->kw;
+      // torch layout: conv [Cout,Cin,k], deconv [Cin,Cout,k]
+      //   fwd conv  : K=A1 (layout 0)   fwd deconv: K=A0 (layout 1)
+      //   bwd conv  : K=A0 (layout 1)   bwd deconv: K=A1 (layout 0)
+      const int layout = (mode == 0) == (d->transposed == 0) ? 0 : 1;
+      const int KPad = pad8(K), NPad = pad32(N);
+      const long total = (long)taps * KPad * NPad;
+      hipLaunchKernelGGL(pack_weight_kernel, dim3(cdiv(total, 256)), block, 0, st, w_src, w_packed, K, N, KPad, NPad, taps, layout,
+                         total);
+    }
+  }
   return ssbev_launch_status();
 }
 
@@ -4487,171 +4526,80 @@ int ssbev_conv_fwd(const float* x, const float* w_packed, const float* bias, flo
                    const ssbev_conv_dims* d, ssbev_stream_t stream) {
   if (!conv_dims_ok(d) || !x || !w_packed || !y) return SSBEV_EINVAL;
   if (ssbev_bf16::storage_mode(d)) return SSBEV_EINVAL;      // bf16 tensors go through ssbev_conv_fwd_bf16 (typed pointers)
-  if (ssbev_thin::thinin_applicable(d, 0)) return ssbev_thin::thinin_launch(x, w_packed, bias, y, d, 0, as_stream(stream));
-  if (d->Cin % 4 != 0) return SSBEV_EINVAL;   // float4 channel loads: caller pads K channels to 4
-  if (conv_thin_applicable(d, 0)) return launch_conv_thin(x, w_packed, bias, y, d, 0, as_stream(stream));
-  if (conv_tap2_applicable(d, 0)) return launch_conv_tap2(x, w_packed, bias, y, d, 0, as_stream(stream));
-  if (conv_tap2up_applicable(d, 0)) return launch_conv_tap2up(x, w_packed, bias, y, d, 0, as_stream(stream));
-  if (conv_pw32_applicable(d, 0)) return launch_conv_pw32(x, w_packed, bias, y, d, 0, as_stream(stream));
-  if (conv_tapdh_applicable(d, 0)) return launch_conv_tapdh(x, w_packed, bias, y, d, 0, as_stream(stream));
-  if (conv_taph_applicable(d, 0)) return launch_conv_taph(x, w_packed, bias, y, d, 0, as_stream(stream));
-  if (conv_tap_applicable(d, 0)) return launch_conv_tap(x, w_packed, bias, y, d, 0, as_stream(stream));
-  ConvGeom g;
-  g.B = d->B; g.Cin = d->Cin; g.Cout = d->Cout; g.CinPad = pad8(d->Cin); g.CoutPad = pad32(d->Cout);
-  g.Di = d->Di; g.Hi = d->Hi; g.Wi = d->Wi; g.Do = d->Do; g.Ho = d->Ho; g.Wo = d->Wo;
-  g.kd = d->kd; g.kh = d->kh; g.kw = d->kw; g.sd = d->sd; g.sh = d->sh; g.sw = d->sw;
-  g.pd = d->pd; g.ph = d->ph; g.pw = d->pw; g.dd = d->dd; g.dh = d->dh; g.dw = d->dw;
-  g.form = d->transposed ? 1 : 0; g.relu = d->relu; g.accumulate = d->accumulate;
-  g.hint = d->tile_hint >= 10 ? d->tile_hint : 0;       // hints below 10 select other kernel families
-  g.chunk_taps = 0; g.bf16 = d->precision == 1;
-  return dispatch_gather(x, w_packed, bias, y, g, as_stream(stream));
+  return run_conv(x, w_packed, bias, y, d, 0, as_stream(stream));
 }
 
 int ssbev_conv_bwd_data(const float* gy, const float* w_packed_t, float* gx,
                         const ssbev_conv_dims* d, ssbev_stream_t stream) {
   if (!conv_dims_ok(d) || !gy || !w_packed_t || !gx) return SSBEV_EINVAL;
   if (ssbev_bf16::storage_mode(d)) return SSBEV_EINVAL;      // -> ssbev_conv_bwd_data_bf16
-  if (ssbev_thin::thinin_applicable(d, 1)) return ssbev_thin::thinin_launch(gy, w_packed_t, nullptr, gx, d, 1, as_stream(stream));
-  if (conv_thin_applicable(d, 1)) return launch_conv_thin(gy, w_packed_t, nullptr, gx, d, 1, as_stream(stream));
-  if (conv_tap2_applicable(d, 1)) return launch_conv_tap2(gy, w_packed_t, nullptr, gx, d, 1, as_stream(stream));
-  if (conv_tap2up_applicable(d, 1)) return launch_conv_tap2up(gy, w_packed_t, nullptr, gx, d, 1, as_stream(stream));
-  if (conv_pw32_applicable(d, 1)) return launch_conv_pw32(gy, w_packed_t, nullptr, gx, d, 1, as_stream(stream));
-  if (conv_tapdh_applicable(d, 1)) return launch_conv_tapdh(gy, w_packed_t, nullptr, gx, d, 1, as_stream(stream));
-  if (conv_taph_applicable(d, 1)) return launch_conv_taph(gy, w_packed_t, nullptr, gx, d, 1, as_stream(stream));
-  if (conv_tap_applicable(d, 1)) return launch_conv_tap(gy, w_packed_t, nullptr, gx, d, 1, as_stream(stream));
-  ConvGeom g;   // roles swapped: source grid = forward output grid, K = Cout, N = Cin
-  g.B = d->B; g.Cin = d->Cout; g.Cout = d->Cin; g.CinPad = pad8(d->Cout); g.CoutPad = pad32(d->Cin);
-  g.Di = d->Do; g.Hi = d->Ho; g.Wi = d->Wo; g.Do = d->Di; g.Ho = d->Hi; g.Wo = d->Wi;
-  g.kd = d->kd; g.kh = d->kh; g.kw = d->kw; g.sd = d->sd; g.sh = d->sh; g.sw = d->sw;
-  g.pd = d->pd; g.ph = d->ph; g.pw = d->pw; g.dd = d->dd; g.dh = d->dh; g.dw = d->dw;
-  g.form = d->transposed ? 0 : 1;   // grad of a conv gathers like a deconv and vice versa
-  g.relu = 0; g.accumulate = d->accumulate; g.hint = d->tile_hint >= 10 ? d->tile_hint : 0; g.chunk_taps = 0;
-  g.bf16 = d->precision == 1;
-  if (g.Cin % 4 != 0) return SSBEV_EINVAL;
-  return dispatch_gather(gy, w_packed_t, nullptr, gx, g, as_stream(stream));
+  return run_conv(gy, w_packed_t, nullptr, gx, d, 1, as_stream(stream));
 }
 
 size_t ssbev_conv_bwd_weight_workspace(const ssbev_conv_dims* d) {
-  if (!conv_dims_ok(d)) return 0;
-  if (ssbev_bf16::storage_mode(d)) return ssbev_bf16::wgrad_workspace(d);
-  if (ssbev_thin::wgrad_applicable(d)) return ssbev_thin::wgrad_workspace(d);
-  {
-    const WgradThinPlan tp = plan_wgrad_thin(d);
-    if (tp.ok) return align256b((size_t)tp.nchunks * 27 * d->Cin * d->Cout * sizeof(float));
-  }
-  {
-    const Wgrad1x1Plan p1 = plan_wgrad_1x1(d);
-    if (p1.ok && d->tile_hint != 7) return align256b((size_t)p1.nchunks * p1.Cq * p1.Cp * sizeof(float));
-  }
-  {
-    const WgradDhPlan hp = plan_wgrad_dh(d);
-    if (hp.ok) return wgrad_dh_workspace(hp);
-  }
-  {
-    const WgradLdsPlan lp = plan_wgrad_lds(d);
-    if (lp.ok && d->tile_hint != 7)
-      return align256b((size_t)lp.nchunks * lp.ksplit * d->kd * 9 * d->Cout * d->Cin * sizeof(float));
-  }
-  if (wgrad_cf_applicable(d)) {
-    WgradCfg c;
-    const WgradCfGeom g = make_wgrad_cf_geom(d, &c);
-    const size_t N = (size_t)g.B * g.D * g.H * g.W;
-    return align256b((size_t)g.nchunks * d->kd * d->kh * d->kw * g.Cp * g.Cq * sizeof(float)) +
-           align256b((size_t)g.Cp * N * sizeof(float)) +
-           align256b(((size_t)g.Cq * g.B * g.Dp * g.Hp * g.Wp + 16) * sizeof(float));
-  }
-  const WgradGeom g = make_wgrad_geom(d);
-  return (size_t)g.nchunks * d->kd * d->kh * d->kw * g.Cp * g.Cq * sizeof(float);
+  return conv_dims_ok(d) ? select_wgrad(d).ws_bytes : 0;
 }
 
 int ssbev_conv_bwd_weight(const float* x, const float* gy, float* gw, const ssbev_conv_dims* d,
                           void* ws, size_t ws_bytes, ssbev_stream_t stream) {
   if (!conv_dims_ok(d) || !x || !gy || !gw || !ws) return SSBEV_EINVAL;
   if (ssbev_bf16::storage_mode(d)) return SSBEV_EINVAL;      // -> ssbev_conv_bwd_weight_bf16
-  if (ws_bytes < ssbev_conv_bwd_weight_workspace(d)) return SSBEV_EWORKSPACE;
-  if (ssbev_thin::wgrad_applicable(d)) return ssbev_thin::wgrad_launch(x, gy, gw, d, ws, ws_bytes, as_stream(stream));
-  {
-    const WgradThinPlan tp = plan_wgrad_thin(d);
-    if (tp.ok) {                                 // 32 -> (<= 4) heads: VALU reduction over the LDS ring
-      hipStream_t st = as_stream(stream);
-      float* partial = static_cast<float*>(ws);
-      const size_t lds = (size_t)(kTapRingF + 2 * kTapWseg * kThinNP) * sizeof(float);
-      hipLaunchKernelGGL(wgrad_thin_kernel, dim3(tp.nchunks), dim3(256), lds, st, x, gy, partial, tp.g);
-      launch_wgrad_reduce(partial, gw, tp.nchunks, 27, d->Cin, d->Cout, st);
-      return ssbev_launch_status();
-    }
-  }
-  {
-    const Wgrad1x1Plan p1 = plan_wgrad_1x1(d);
-    if (p1.ok && d->tile_hint != 7) {
-      hipStream_t st = as_stream(stream);
-      const float* P = d->transposed ? x : gy;
-      const float* Q = d->transposed ? gy : x;
-      float* partial = static_cast<float*>(ws);
-      dim3 grid(p1.nchunks, cdiv(p1.Cq, 32 * p1.MQ) * cdiv(p1.Cp, 32 * p1.MP)), block(1024);
-      if (p1.MQ == 2 && p1.MP == 2)
-        hipLaunchKernelGGL((wgrad_1x1_kernel<2, 2>), grid, block, 0, st, P, Q, partial, p1.N, p1.Cq, p1.Cp, p1.chunk, p1.nchunks);
-      else if (p1.MQ == 2)
-        hipLaunchKernelGGL((wgrad_1x1_kernel<2, 1>), grid, block, 0, st, P, Q, partial, p1.N, p1.Cq, p1.Cp, p1.chunk, p1.nchunks);
-      else if (p1.MP == 2)
-        hipLaunchKernelGGL((wgrad_1x1_kernel<1, 2>), grid, block, 0, st, P, Q, partial, p1.N, p1.Cq, p1.Cp, p1.chunk, p1.nchunks);
-      else
-        hipLaunchKernelGGL((wgrad_1x1_kernel<1, 1>), grid, block, 0, st, P, Q, partial, p1.N, p1.Cq, p1.Cp, p1.chunk, p1.nchunks);
-      launch_wgrad_reduce(partial, gw, p1.nchunks, 1, p1.Cq, p1.Cp, st);
-      return ssbev_launch_status();
-    }
-  }
-  {
-    const WgradDhPlan hp = plan_wgrad_dh(d);   // <= 32 x 32 channels, even D and H: F(2,3) along d and h (round 4)
-    if (hp.ok) return run_wgrad_dh(x, gy, gw, hp, ws, as_stream(stream));
-  }
-  {
-    const WgradLdsPlan lp = plan_wgrad_lds(d);
-    if (lp.ok && d->tile_hint != 7) {          // tile_hint 7: force the channel-major path (tests / A-B timing)
-      hipStream_t st = as_stream(stream);
-      float* partial = static_cast<float*>(ws);
-      const int rc = run_wgrad_lds(x, gy, partial, d, lp, st);
-      if (rc != SSBEV_OK) return rc;
-      launch_wgrad_reduce(partial, gw, lp.nchunks * lp.ksplit, d->kd * 9, lp.g.Cq, lp.g.Cp, st);
-      return ssbev_launch_status();
-    }
-  }
-  if (wgrad_cf_applicable(d)) {
-    hipStream_t st = as_stream(stream);
-    WgradCfg c;
-    const WgradCfGeom g = make_wgrad_cf_geom(d, &c);
-    const size_t N = (size_t)g.B * g.D * g.H * g.W;
-    const int taps = g.kd * g.kh * g.kw;
-    char* base = static_cast<char*>(ws);
-    float* partial = reinterpret_cast<float*>(base);
-    float* Pt = reinterpret_cast<float*>(base + align256b((size_t)g.nchunks * taps * g.Cp * g.Cq * sizeof(float)));
-    float* Qp = reinterpret_cast<float*>(reinterpret_cast<char*>(Pt) + align256b((size_t)g.Cp * N * sizeof(float)));
-    const size_t qbytes = ((size_t)g.Cq * g.B * g.Dp * g.Hp * g.Wp + 16) * sizeof(float);
-    if (hipMemsetAsync(Qp, 0, qbytes, st) != hipSuccess) return SSBEV_ELAUNCH;
-    hipLaunchKernelGGL(transpose_pad_kernel, dim3(cdiv(N, 64), cdiv(g.Cp, 32)), dim3(256), 0, st, gy, Pt, g.Cp, g.B,
-                       g.D, g.H, g.W, 0, 0, 0, g.D, g.H, g.W);
-    hipLaunchKernelGGL(transpose_pad_kernel, dim3(cdiv(N, 64), cdiv(g.Cq, 32)), dim3(256), 0, st, x, Qp, g.Cq, g.B,
-                       g.D, g.H, g.W, d->pd, d->ph, d->pw, g.Dp, g.Hp, g.Wp);
-    if (c.TH == 1 && c.TW == 1) launch_wgrad_cf<2, 2, 1, 1>(Pt, Qp, partial, g, st);
-    else if (c.MQ == 2) launch_wgrad_cf<2, 2, 1, 3>(Pt, Qp, partial, g, st);
-    else if (c.TH == 3) launch_wgrad_cf<1, 1, 3, 3>(Pt, Qp, partial, g, st);
-    else launch_wgrad_cf<1, 1, 1, 3>(Pt, Qp, partial, g, st);
-    launch_wgrad_reduce(partial, gw, g.nchunks, taps, g.Cq, g.Cp, st);
-    return ssbev_launch_status();
-  }
-  const WgradGeom g = make_wgrad_geom(d);
-  const float* P = d->transposed ? x : gy;
-  const float* Qt = d->transposed ? gy : x;
+  const WgradPlan p = select_wgrad(d);
+  if (ws_bytes < p.ws_bytes) return SSBEV_EWORKSPACE;
   hipStream_t st = as_stream(stream);
-  const int taps = g.kd * g.kh * g.kw;
-  if ((long)g.B * g.Ds * g.Hs * g.Ws >= (1L << 31)) return SSBEV_EINVAL;
-  const WgradCfg c = wgrad_cfg(g.Cp, g.Cq, g.kh, g.kw);
-  float* wsf = static_cast<float*>(ws);
-  if (c.TH == 1 && c.TW == 1) launch_wgrad<2, 2, 1, 1>(P, Qt, wsf, g, st);
-  else if (c.MQ == 2) launch_wgrad<2, 2, 1, 3>(P, Qt, wsf, g, st);
-  else if (c.TH == 3) launch_wgrad<1, 1, 3, 3>(P, Qt, wsf, g, st);
-  else launch_wgrad<1, 1, 1, 3>(P, Qt, wsf, g, st);
-  launch_wgrad_reduce(wsf, gw, g.nchunks, taps, g.Cq, g.Cp, st);
+  char* base = static_cast<char*>(ws);
+  float* partial = static_cast<float*>(ws);
+  // P is the tensor on the coarse grid, Q the one the taps slide over (1x1 and direct kernels; run_wgrad_lds swaps for itself)
+  const float* P = d->transposed ? x : gy;
+  const float* Q = d->transposed ? gy : x;
+  switch (p.kind) {
+    case WgradKind::Bf16Storage: return SSBEV_EINVAL;
+    case WgradKind::ThinSide: return ssbev_thin::wgrad_launch(x, gy, gw, d, ws, ws_bytes, st);
+    case WgradKind::Thin: {                      // 32 -> (<= 4) heads: VALU reduction over the LDS ring
+      const size_t lds = (size_t)(kTapRingF + 2 * kTapWseg * kThinNP) * sizeof(float);
+      hipLaunchKernelGGL(wgrad_thin_kernel, dim3(p.thin.nchunks), dim3(256), lds, st, x, gy, partial, p.thin.g);
+      launch_wgrad_reduce(partial, gw, p.thin.nchunks, 27, d->Cin, d->Cout, st);
+      break;
+    }
+    case WgradKind::Pointwise: {
+      const Wgrad1x1Plan& p1 = p.p1;
+      dim3 grid(p1.nchunks, cdiv(p1.Cq, 32 * p1.MQ) * cdiv(p1.Cp, 32 * p1.MP)), block(1024);
+      with_wgrad_1x1_tile(p1, [&](auto mq, auto mp) {
+        hipLaunchKernelGGL((wgrad_1x1_kernel<mq(), mp()>), grid, block, 0, st, P, Q, partial, p1.N, p1.Cq, p1.Cp, p1.chunk, p1.nchunks);
+      });
+      launch_wgrad_reduce(partial, gw, p1.nchunks, 1, p1.Cq, p1.Cp, st);
+      break;
+    }
+    case WgradKind::Dh:                          // <= 32 x 32 channels, even D and H: F(2,3) along d and h
+      return run_wgrad_dh(x, gy, gw, p.dh, partial, reinterpret_cast<float*>(base + p.gu_off), st);
+    case WgradKind::Lds: {
+      const int rc = run_wgrad_lds(x, gy, partial, d, p.lds, st);
+      if (rc != SSBEV_OK) return rc;
+      launch_wgrad_reduce(partial, gw, p.lds.nchunks * p.lds.ksplit, d->kd * 9, p.lds.g.Cq, p.lds.g.Cp, st);
+      break;
+    }
+    case WgradKind::ChannelsFirst: {
+      const WgradCfGeom& g = p.cf;
+      const size_t N = (size_t)g.B * g.D * g.H * g.W;
+      float* Pt = reinterpret_cast<float*>(base + p.pt_off);
+      float* Qp = reinterpret_cast<float*>(base + p.qp_off);
+      if (hipMemsetAsync(Qp, 0, p.qp_bytes, st) != hipSuccess) return SSBEV_ELAUNCH;
+      hipLaunchKernelGGL(transpose_pad_kernel, dim3(cdiv(N, 64), cdiv(g.Cp, 32)), dim3(256), 0, st, gy, Pt, g.Cp, g.B,
+                         g.D, g.H, g.W, 0, 0, 0, g.D, g.H, g.W);
+      hipLaunchKernelGGL(transpose_pad_kernel, dim3(cdiv(N, 64), cdiv(g.Cq, 32)), dim3(256), 0, st, x, Qp, g.Cq, g.B,
+                         g.D, g.H, g.W, d->pd, d->ph, d->pw, g.Dp, g.Hp, g.Wp);
+      with_wgrad_cfg(p.cfg, [&](auto mq, auto mp, auto th, auto tw) { launch_wgrad_cf<mq(), mp(), th(), tw()>(Pt, Qp, partial, g, st); });
+      launch_wgrad_reduce(partial, gw, g.nchunks, g.kd * g.kh * g.kw, g.Cq, g.Cp, st);
+      break;
+    }
+    case WgradKind::Direct: {
+      const WgradGeom& g = p.direct;
+      if ((long)g.B * g.Ds * g.Hs * g.Ws >= (1L << 31)) return SSBEV_EINVAL;
+      with_wgrad_cfg(p.cfg, [&](auto mq, auto mp, auto th, auto tw) { launch_wgrad<mq(), mp(), th(), tw()>(P, Q, partial, g, st); });
+      launch_wgrad_reduce(partial, gw, g.nchunks, g.kd * g.kh * g.kw, g.Cq, g.Cp, st);
+      break;
+    }
+  }
   return ssbev_launch_status();
 }
 
