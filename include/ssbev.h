@@ -759,6 +759,26 @@ int ssbev_wino43_df_gemm(const float* P, const float* Wp, float* Mo, const ssbev
 size_t ssbev_wino43_df_wgrad_workspace(const ssbev_wino_dims* d, int N);
 int ssbev_wino43_df_wgrad(const float* P, const float* Z, float* gw, const ssbev_wino_dims* d, int N, void* workspace,
                           size_t ws_bytes, ssbev_stream_t stream);
+/* Host-side plan query (since ssbev_version() 108; no device work): the kernel instance and launch geometry of
+ * ssbev_wino43_df_gemm (first group) and ssbev_wino43_df_wgrad (w_ group) for these dims, from the plan functions the launchers,
+ * ssbev_wino43_df_instance and ssbev_wino43_df_wgrad_workspace themselves read.  SSBEV_EINVAL for a NULL argument and for dims
+ * ssbev_wino43_df_supported refuses.  (ssbev_wino43_df_wgrad additionally refuses B D (H/4) (W/4) max(K, N) >= 2^31.) */
+typedef struct {
+  int mt, nw;               /* wino_df_kernel<MT, NW>: 32-row tiles per wave, waves per workgroup (instance = 10 mt + nw) */
+  int ncolgrp, nrowgrp;     /* column groups of 32 nw columns, row groups of 32 mt hw-tiles per (b, depth tile) */
+  int nst;                  /* k-stages of 32 channels */
+  int64_t grid;             /* workgroups = 36 B (D/2) nrowgrp ncolgrp */
+  size_t lds_bytes;         /* dynamic LDS per workgroup */
+  int w_kw, w_nt, w_br;     /* wino_dfw_kernel<KW, NT, BR>: k-waves, 32-column tiles per wave, rows per stage */
+  int w_nkb, w_nnb;         /* blocks of 32 kw channels / (4 / kw) nt 32 columns */
+  int w_nchunk;             /* row chunks (partial sums; > 1: wino_dfw_sum_kernel runs) */
+  int w_stages_per_chunk;   /* stages of a chunk (the last chunk may be shorter) */
+  int w_total_stages;       /* B (D/2) ceil((H/4)(W/4) / br) */
+  int64_t w_grid;           /* workgroups = 36 nchunk nkb nnb */
+  size_t w_lds_bytes;       /* dynamic LDS per workgroup */
+  size_t w_workspace;       /* bytes, what ssbev_wino43_df_wgrad_workspace returns */
+} ssbev_wino43_df_plan;
+int ssbev_wino43_df_plan_query(const ssbev_wino_dims* d, int N, ssbev_wino43_df_plan* out);
 
 #ifdef __cplusplus
 }

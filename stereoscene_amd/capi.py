@@ -110,6 +110,13 @@ class GemmPlan(C.Structure):
                 ("grid", C.c_int64), ("workspace", C.c_size_t)]
 
 
+class Wino43DfPlan(C.Structure):
+    _fields_ = [("mt", C.c_int), ("nw", C.c_int), ("ncolgrp", C.c_int), ("nrowgrp", C.c_int), ("nst", C.c_int), ("grid", C.c_int64),
+                ("lds_bytes", C.c_size_t), ("w_kw", C.c_int), ("w_nt", C.c_int), ("w_br", C.c_int), ("w_nkb", C.c_int),
+                ("w_nnb", C.c_int), ("w_nchunk", C.c_int), ("w_stages_per_chunk", C.c_int), ("w_total_stages", C.c_int),
+                ("w_grid", C.c_int64), ("w_lds_bytes", C.c_size_t), ("w_workspace", C.c_size_t)]
+
+
 class JitterParams(C.Structure):
     _fields_ = [("flags", C.c_int), ("mode", C.c_int), ("delta", C.c_float), ("alpha", C.c_float), ("saturation", C.c_float),
                 ("hue", C.c_float), ("perm", C.c_int * 3)]
@@ -229,6 +236,7 @@ SIGNATURES = {
     "ssbev_wino43_df_gemm": (C.c_int, [_P, _P, _P, C.POINTER(WinoDims), C.c_int, _P]),
     "ssbev_wino43_df_wgrad_workspace": (C.c_size_t, [C.POINTER(WinoDims), C.c_int]),
     "ssbev_wino43_df_wgrad": (C.c_int, [_P, _P, _P, C.POINTER(WinoDims), C.c_int, _P, C.c_size_t, _P]),
+    "ssbev_wino43_df_plan_query": (C.c_int, [C.POINTER(WinoDims), C.c_int, C.POINTER(Wino43DfPlan)]),
     "ssbev_wino2d_input_transform": (C.c_int, [_P, _P, C.POINTER(WinoDims), _P]),
     "ssbev_wino2d_output_transform": (C.c_int, [_P, _P, C.POINTER(WinoDims), _P]),
     "ssbev_wino2d_output_adjoint": (C.c_int, [_P, _P, C.POINTER(WinoDims), _P]),

@@ -546,9 +546,12 @@ int ssbev_wino43_df_pack(const float* w, float* Wp, int Cout, int Cin, int mode,
   return ssbev_launch_status();
 }
 
-// Template instance <MT, NW> of wino_df_kernel for a problem (also reported by ssbev_wino43_df_instance, so that a profiler can
-// attribute launches to kernel symbols)
-static void df_instance(const ssbev_wino_dims* d, int N, int& mt, int& nw) {
+// Template instance <MT, NW> of wino_df_kernel for a problem and the geometry its launch runs with: read by the launcher, by
+// ssbev_wino43_df_instance (so that a profiler can attribute launches to kernel symbols) and by ssbev_wino43_df_plan_query
+struct DfPlan { int mt, nw, ncolgrp, nrowgrp, nst; long grid; size_t lds; };
+
+static DfPlan df_instance(const ssbev_wino_dims* d, int N) {
+  int mt, nw;
   const int ntile = ((N + 31) & ~31) / 32, Thw = (d->H / 4) * (d->W / 4), ND = d->D / 2;
   // waves per workgroup: the largest of 4, 3, 2 that wastes no column tile (N = 192 -> 3, 128 / 256 / 512 -> 4)
   static const int forced_nw = env_int("SSBEV_DF_NW", 0), forced_mt = env_int("SSBEV_DF_MT", 0);
@@ -572,13 +575,20 @@ static void df_instance(const ssbev_wino_dims* d, int N, int& mt, int& nw) {
   if (forced_mt == 1 || forced_mt == 2) mt = forced_mt;
   const int key = mt * 10 + nw;
   if (key != 24 && key != 23 && key != 22 && key != 14 && key != 13 && key != 12) { mt = 1; nw = 2; }     // the launcher's default case
+  DfPlan p;
+  p.mt = mt; p.nw = nw;
+  p.ncolgrp = (ntile + nw - 1) / nw;
+  p.nrowgrp = (Thw + 32 * mt - 1) / (32 * mt);
+  p.nst = d->C / DF_BK;
+  p.grid = (long)36 * d->B * ND * p.nrowgrp * p.ncolgrp;
+  p.lds = (size_t)2 * 4 * 32 * mt * DF_BK * sizeof(float);        // 64 KiB (MT = 2) / 32 KiB
+  return p;
 }
 
 int ssbev_wino43_df_instance(const ssbev_wino_dims* d, int N) {
   if (!df_dims_ok(d, N)) return 0;
-  int mt, nw;
-  df_instance(d, N, mt, nw);
-  return mt * 10 + nw;
+  const DfPlan p = df_instance(d, N);
+  return p.mt * 10 + p.nw;
 }
 
 // P [36][B*D*Thw][K] = ssbev_wino43_2d_input_transform(x), Wp = ssbev_wino43_df_pack(...), Mo [36][B*D*Thw][N];
@@ -588,15 +598,14 @@ int ssbev_wino43_df_gemm(const float* P, const float* Wp, float* Mo, const ssbev
   DfGeom g;
   g.B = d->B; g.D = d->D; g.Thw = (d->H / 4) * (d->W / 4); g.K = d->C; g.N = N; g.NPad = (N + 31) & ~31;
   g.ND = d->D / 2;
-  const int ntile = g.NPad / 32;
-  int mt, nw;
-  df_instance(d, N, mt, nw);
-  g.ncolgrp = (ntile + nw - 1) / nw;
-  g.nrowgrp = (g.Thw + 32 * mt - 1) / (32 * mt);
+  const DfPlan pl = df_instance(d, N);
+  const int mt = pl.mt, nw = pl.nw;
+  g.ncolgrp = pl.ncolgrp;
+  g.nrowgrp = pl.nrowgrp;
   g.NU = g.B * g.ND * g.nrowgrp;
   g.nxi = 36;
-  const size_t lds = (size_t)2 * 4 * 32 * mt * DF_BK * sizeof(float);        // 64 KiB (MT = 2) / 32 KiB
-  const long nwg = (long)g.nxi * g.NU * g.ncolgrp;
+  const size_t lds = pl.lds;
+  const long nwg = pl.grid;
   hipStream_t st = as_stream(stream);
 #ifdef SSBEV_DF_CLOCKS
 #define DF_CLOCKS_BEGIN(NW_)                                                                                               \
@@ -643,7 +652,7 @@ int ssbev_wino43_df_gemm(const float* P, const float* Wp, float* Mo, const ssbev
 
 // Weight gradient.  P [36][B*D*Thw][K] (saved by the forward), Z [36][B*D*Thw][N] = ssbev_wino43_2d_output_adjoint(gy),
 // gw [N = Cout][K = Cin][27].  Workspace: ssbev_wino43_df_wgrad_workspace bytes.
-struct DfwPlan { int kw, nt, br, pc, zc, nkb, nnb, nchunk, total_stages; };
+struct DfwPlan { int kw, nt, br, pc, zc, nkb, nnb, nchunk, stages_per_chunk, total_stages; long grid; size_t lds, workspace; };
 
 static DfwPlan dfw_plan(const ssbev_wino_dims* d, int N) {
   DfwPlan p;
@@ -674,12 +683,16 @@ static DfwPlan dfw_plan(const ssbev_wino_dims* d, int N) {
     nchunk = best_n;
   }
   p.nchunk = std::min(nchunk, std::max(1, p.total_stages / 8));
+  p.stages_per_chunk = (p.total_stages + p.nchunk - 1) / p.nchunk;
+  p.grid = (long)per * p.nchunk;
+  p.lds = (size_t)2 * (4 * p.br * p.pc + 2 * p.br * p.zc) * sizeof(float);     // 80 / 44 / 48 KiB
+  p.workspace = (size_t)p.nchunk * 144 * K * N * sizeof(float);                 // part[nchunk][4][36][K][N]
   return p;
 }
 
 size_t ssbev_wino43_df_wgrad_workspace(const ssbev_wino_dims* d, int N) {
   if (!df_dims_ok(d, N)) return 0;
-  return (size_t)dfw_plan(d, N).nchunk * 144 * d->C * N * sizeof(float);
+  return dfw_plan(d, N).workspace;
 }
 
 int ssbev_wino43_df_wgrad(const float* P, const float* Z, float* gw, const ssbev_wino_dims* d, int N, void* ws, size_t ws_bytes,
@@ -687,18 +700,18 @@ int ssbev_wino43_df_wgrad(const float* P, const float* Z, float* gw, const ssbev
   if (!df_dims_ok(d, N) || !P || !Z || !gw || !ws) return SSBEV_EINVAL;
   if (N % 4 != 0) return SSBEV_EINVAL;
   if ((long)d->B * d->D * (d->H / 4) * (d->W / 4) * std::max(d->C, N) >= (1L << 31)) return SSBEV_EINVAL;   // 32-bit slab offsets
-  if (ws_bytes < ssbev_wino43_df_wgrad_workspace(d, N)) return SSBEV_EWORKSPACE;
   const DfwPlan pl = dfw_plan(d, N);
+  if (ws_bytes < pl.workspace) return SSBEV_EWORKSPACE;
   DfwGeom g;
   g.B = d->B; g.D = d->D; g.Thw = (d->H / 4) * (d->W / 4); g.K = d->C; g.N = N;
   g.ND = d->D / 2; g.nrowstage = (g.Thw + pl.br - 1) / pl.br;
   g.nkb = pl.nkb; g.nnb = pl.nnb;
   g.nchunk = pl.nchunk;
-  g.stages_per_chunk = (pl.total_stages + g.nchunk - 1) / g.nchunk;
+  g.stages_per_chunk = pl.stages_per_chunk;
   g.nxi = 36;
-  const size_t lds = (size_t)2 * (4 * pl.br * pl.pc + 2 * pl.br * pl.zc) * sizeof(float);     // 80 / 44 / 48 KiB
+  const size_t lds = pl.lds;
   hipStream_t st = as_stream(stream);
-  const long nwg = (long)g.nxi * g.nchunk * g.nkb * g.nnb;
+  const long nwg = pl.grid;
 #define SSBEV_DFW_LAUNCH(KW_, NT_, BR_)                                                                                       \
   do {                                                                                                                     \
     auto kern = wino_dfw_kernel<KW_, NT_, BR_>;                                                                               \
@@ -717,6 +730,20 @@ int ssbev_wino43_df_wgrad(const float* P, const float* Z, float* gw, const ssbev
   hipLaunchKernelGGL(wino_dfw_reduce_kernel, dim3(cdiv((size_t)g.K * N, 256)), dim3(256), 0, st, static_cast<const float*>(ws), gw,
                      N, g.K);
   return ssbev_launch_status();
+}
+
+// The instance and geometry ssbev_wino43_df_gemm and ssbev_wino43_df_wgrad launch for these dims, from the plan functions the
+// launchers themselves read.  No device work; SSBEV_EINVAL for dims ssbev_wino43_df_supported refuses.
+int ssbev_wino43_df_plan_query(const ssbev_wino_dims* d, int N, ssbev_wino43_df_plan* out) {
+  if (!out || !df_dims_ok(d, N)) return SSBEV_EINVAL;
+  const DfPlan c = df_instance(d, N);
+  const DfwPlan w = dfw_plan(d, N);
+  out->mt = c.mt; out->nw = c.nw; out->ncolgrp = c.ncolgrp; out->nrowgrp = c.nrowgrp; out->nst = c.nst;
+  out->grid = c.grid; out->lds_bytes = c.lds;
+  out->w_kw = w.kw; out->w_nt = w.nt; out->w_br = w.br; out->w_nkb = w.nkb; out->w_nnb = w.nnb;
+  out->w_nchunk = w.nchunk; out->w_stages_per_chunk = w.stages_per_chunk; out->w_total_stages = w.total_stages;
+  out->w_grid = w.grid; out->w_lds_bytes = w.lds; out->w_workspace = w.workspace;
+  return SSBEV_OK;
 }
 
 }  // extern "C"
