@@ -580,6 +580,30 @@ int ssbev_depth_bce_fwd(const float* gt_depths, const float* depth_pred, float* 
 int ssbev_depth_bce_bwd(const float* depth_pred, const float* grad_loss, const float* out2, float* grad_pred, int BN, int D, int fH,
                         int fW, int ds, float c0, float dd, float weight, const void* ws, ssbev_stream_t stream);
 
+/* Depth KL loss (since ssbev_version() 109; ViewTransformerLSSVoxel.py:390-416 get_klv_depth_loss with
+ * utils/gaussian.py:90-130 generate_guassian_depth_target, constant_std): same tensors as the BCE form; dbound = (d0, d1, dd) as
+ * the config gives it, in double.  Per feature pixel m = the smallest non-zero depth of its ds x ds block (0 when it has none);
+ * the row is foreground when (float)d0 <= m <= (float)(d1 - dd); its target over the D bins is
+ *   t_d = cdf(x_{d+1}) - cdf(x_d),  x_i = (d0 - dd / 2) + i dd (i = 0..D, rounded to fp32 once),
+ *   cdf(x) = 0.5 (1 + erf(((x * edge_scale - m / dd) / (sigma / dd)) / sqrt 2)),  all in fp32,
+ * sigma = the standard deviation in metres (the reference's constant_std = 0.5).  edge_scale = 1 is the reference as executed
+ * (the mean is in bin units, the edges are in metres); edge_scale = 1 / dd puts both in bin units.
+ * out2[0] = weight * sum over foreground rows and bins of (xlogy(t, t) - t log(p + 1e-4)) / max(foreground rows, 1), out2[1] =
+ * that divisor; the sum is taken in double in a fixed order (no atomics: the same bits every run).  With no foreground row
+ * out2[0] = 0 and the gradient is all zero (the reference divides 0 by 0).  A t that rounds below zero counts as 0.
+ * The workspace keeps m and the foreground flag per pixel for _bwd, which recomputes t and writes
+ * grad_pred = -(grad_loss[0] * weight / out2[1]) * t / (p + 1e-4) on foreground rows and exactly 0 elsewhere.
+ * SSBEV_EINVAL (before any device work) for a NULL pointer, a non-positive dim, sigma <= 0, dd <= 0, edge_scale <= 0, a non-finite
+ * value, or when ceil((d1 - (d0 - dd / 2)) / dd), the length of torch.arange(d0 - dd / 2, d1, dd), is not D + 1;
+ * SSBEV_EWORKSPACE when ws_bytes is below the query, which answers 0 for refused dims. */
+size_t ssbev_depth_kld_workspace(int BN, int fH, int fW);
+int ssbev_depth_kld_fwd(const float* gt_depths, const float* depth_pred, float* out2, int BN, int D, int fH, int fW, int ds,
+                        double d0, double d1, double dd, float sigma, float edge_scale, float weight, void* ws, size_t ws_bytes,
+                        ssbev_stream_t stream);
+int ssbev_depth_kld_bwd(const float* depth_pred, const float* grad_loss, const float* out2, float* grad_pred, int BN, int D, int fH,
+                        int fW, int ds, double d0, double d1, double dd, float sigma, float edge_scale, float weight, const void* ws,
+                        size_t ws_bytes, ssbev_stream_t stream);
+
 size_t ssbev_lidar_depth_workspace(int H, int W);
 int ssbev_lidar_depth_map(const float* points, int n_points, const float* cam, const float* labels, float* uvd,
                           unsigned char* valid, float* depth, float* seg, int H, int W, void* ws, size_t ws_bytes,

@@ -10,6 +10,7 @@ Tensors are logical NC[D]HW (what the reference modules exchange) held in channe
 which is the layout the kernels read and write; nothing is permuted on the way in or out.
 """
 import ctypes as C
+import math
 
 import os
 
@@ -2374,6 +2375,93 @@ class _DepthBce(torch.autograd.Function):
 
 def depth_bce_loss(gt_depths, depth_pred, ds, dbound, weight):
     return _DepthBce.apply(gt_depths, depth_pred, ds, dbound, weight)
+
+
+DEPTH_KLD = os.environ.get("SSBEV_DEPTH_KLD", "1") != "0"    # fused Gaussian KL depth loss (0 = the tensor expression below)
+DEPTH_KLD_UNITS = ("reference", "bins")
+
+
+def _depth_kld_edge_scale(dbound, units):
+    """1 for "reference" (the executed formula: mean in bin units, edges in metres), 1 / dd for "bins" (both in bin units)."""
+    if units not in DEPTH_KLD_UNITS:
+        raise ValueError(f"units must be one of {DEPTH_KLD_UNITS}, got {units!r}")
+    return 1.0 if units == "reference" else 1.0 / float(dbound[2])
+
+
+class _DepthKld(torch.autograd.Function):
+    """weight * KL(Gaussian target of the down-sampled LiDAR depth || depth_pred) over the foreground pixels (VT:390-416 +
+    utils/gaussian.py:90-130 with constant_std), ``ssbev_depth_kld_fwd / _bwd``: gt_depths [B, N, H, W], depth_pred
+    [B*N, D, H/ds, W/ds] -> 0-dim loss.  Nothing is read back to the host."""
+
+    @staticmethod
+    def forward(ctx, gt_depths, depth_pred, ds, dbound, weight, std, edge_scale):
+        lib = capi.load()
+        B, N, H, W = gt_depths.shape
+        BN, D, fH, fW = depth_pred.shape
+        assert BN == B * N and fH * ds == H and fW * ds == W
+        gt = _f32(gt_depths, "depth_kld").contiguous()
+        pred = _f32(depth_pred, "depth_kld").contiguous()
+        args = (BN, D, fH, fW, int(ds), float(dbound[0]), float(dbound[1]), float(dbound[2]), float(std), float(edge_scale),
+                float(weight))
+        ws = torch.empty(lib.ssbev_depth_kld_workspace(BN, fH, fW), dtype=torch.uint8, device=pred.device)   # kept for backward
+        out = torch.empty(2, dtype=torch.float32, device=pred.device)
+        capi.check(lib.ssbev_depth_kld_fwd(capi.ptr(gt), capi.ptr(pred), capi.ptr(out), *args, capi.ptr(ws), ws.numel(),
+                                           capi.stream()), "ssbev_depth_kld_fwd")
+        ctx.save_for_backward(pred, out, ws)
+        ctx.args = args
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = capi.load()
+        pred, out, ws = ctx.saved_tensors
+        gp = torch.empty_like(pred)
+        gl = g.to(torch.float32).reshape(1).contiguous()
+        capi.check(lib.ssbev_depth_kld_bwd(capi.ptr(pred), capi.ptr(gl), capi.ptr(out), capi.ptr(gp), *ctx.args, capi.ptr(ws),
+                                           ws.numel(), capi.stream()), "ssbev_depth_kld_bwd")
+        return None, gp, None, None, None, None, None
+
+
+def depth_kld_loss_tensor(gt_depths, depth_pred, ds, dbound, weight, std=0.5, units="reference"):
+    """The Gaussian KL depth loss in ATen ops, on any device (fp32; float64 when ``depth_pred`` is float64): the reference's
+    ``generate_guassian_depth_target(..., constant_std=std)`` + ``get_klv_depth_loss`` operation by operation, except that the
+    background rows are masked instead of gathered away with a boolean index (a nonzero() + host synchronisation): their target
+    and their prediction are replaced by constants, so their terms and gradients vanish exactly.  A target that rounds below
+    zero counts as 0, and no foreground row at all gives 0 instead of the reference's 0 / 0."""
+    es = _depth_kld_edge_scale(dbound, units)
+    d0, d1, dd = (float(v) for v in dbound)
+    if not (dd > 0 and std > 0):
+        raise ValueError(f"dbound step and std must be positive, got {dd}, {std}")
+    B, N, H, W = gt_depths.shape
+    BN, D, fH, fW = depth_pred.shape
+    assert BN == B * N and fH * ds == H and fW * ds == W
+    dt = torch.float64 if depth_pred.dtype == torch.float64 else torch.float32
+    dev = depth_pred.device
+    x = torch.arange(d0 - dd / 2, d1, dd, dtype=dt, device=dev)
+    if x.numel() != D + 1:
+        raise ValueError(f"dbound {tuple(dbound)} gives {x.numel()} edges, depth_pred has {D} bins")
+    g = gt_depths.to(dt).reshape(BN, fH, ds, fW, ds).permute(0, 1, 3, 2, 4).reshape(-1, ds * ds)
+    m = torch.where(g != 0, g, torch.full_like(g, 1e10)).min(dim=-1).values
+    m = torch.where(m == 1e10, torch.zeros_like(m), m)
+    fg = (m >= d0) & (m <= (d1 - dd))
+    rs = (torch.full((), std, dtype=dt, device=dev) / dd).reciprocal()
+    cdf = 0.5 * (1 + torch.erf((x * es - (m / dd).unsqueeze(1)) * rs / math.sqrt(2)))
+    mask = fg.unsqueeze(1)
+    t = torch.where(mask, (cdf[:, 1:] - cdf[:, :-1]).clamp_min(0), torch.zeros((), dtype=dt, device=dev))
+    p = depth_pred.to(dt).permute(0, 2, 3, 1).reshape(-1, D)
+    logp = torch.log(torch.where(mask, p, torch.ones_like(p)) + 1e-4)
+    kl = torch.xlogy(t, t) - t * logp
+    return weight * (kl.sum() / fg.sum().to(dt).clamp(min=1.0))
+
+
+def depth_kld_loss(gt_depths, depth_pred, ds, dbound, weight, std=0.5, units="reference"):
+    """``loss_depth_type="kld"``: fp32 CUDA tensors with ``DEPTH_KLD`` on run on the fused HIP path, anything else (CPU, other
+    dtypes, the switch off) on ``depth_kld_loss_tensor``."""
+    es = _depth_kld_edge_scale(dbound, units)
+    if (DEPTH_KLD and depth_pred.is_cuda and gt_depths.is_cuda and depth_pred.dtype == torch.float32
+            and gt_depths.dtype == torch.float32):
+        return _DepthKld.apply(gt_depths, depth_pred, ds, dbound, weight, std, es)
+    return depth_kld_loss_tensor(gt_depths, depth_pred, ds, dbound, weight, std, units)
 
 
 OCC_TAIL = os.environ.get("SSBEV_OCC_TAIL", "1") != "0"      # scalar loss algebra in one launch (0 = ~110 tiny ATen ops)

@@ -14,10 +14,11 @@ def image_branch_cfg(arch="b7"):
                       out_channels=[128, 128, 128, 128, 128]))
 
 
-def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False):
+def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False, loss_depth_type="bce"):
     """Same structure and hyper-parameters as the reference config's ``model`` dict for the sizes in ``cfg`` (a
     synthetic.CFG_*).  ``image_branch=False`` (default, the benchmarked hot path a1-a16) leaves the 2-D
-    image backbone/neck out: the detector then takes the image-neck features in place of raw images."""
+    image backbone/neck out: the detector then takes the image-neck features in place of raw images.  ``loss_depth_type``:
+    "bce" (the reference config's value) or "kld"."""
     norm_cfg = dict(type="GN", num_groups=32, requires_grad=True)
     channels = [128, 256, 512]
     return dict(
@@ -26,7 +27,7 @@ def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False):
             type="ViewTransformerLiftSplatShootVoxel", downsample=cfg["downsample"], numC_input=640,
             cam_channels=30, semkitti=False, loss_depth_weight=1.0, grid_config=S.grid_config(cfg),
             data_config=dict(input_size=tuple(cfg["input_size"])), numC_Trans=numC_Trans, vp_megvii=False,
-            warp_align_corners=warp_align_corners),
+            warp_align_corners=warp_align_corners, loss_depth_type=loss_depth_type),
         img_bev_encoder_backbone=dict(type="CustomResNet3D", depth=18, num_stage=3, n_input_channels=numC_Trans,
                                       block_inplanes=channels, out_indices=(0, 1, 2), norm_cfg=norm_cfg),
         img_bev_encoder_neck=dict(type="SECONDFPN3D", norm_cfg=norm_cfg, in_channels=channels,

@@ -505,10 +505,13 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
                  point_xyz_mode="cat", cam_channels=27, loss_depth_reg_weight=0.0, use_voxel_net=False,
                  grid_config=None, data_config=None, numC_input=512, numC_Trans=64, downsample=16,
                  accelerate=False, use_bev_pool=True, vp_megvii=False, vp_stero=False,
-                 warp_align_corners=True, ablation="full", **kwargs):
+                 warp_align_corners=True, ablation="full", depth_kld_units="reference", **kwargs):
         super().__init__()
         if ablation not in self.ABLATIONS:
             raise ValueError(f"ablation must be one of {self.ABLATIONS}, got {ablation!r}")
+        if depth_kld_units not in F.DEPTH_KLD_UNITS:
+            raise ValueError(f"depth_kld_units must be one of {F.DEPTH_KLD_UNITS}, got {depth_kld_units!r}")
+        self.depth_kld_units = depth_kld_units
         self.ablation = ablation
         if imgseg or point_xyz_channel or use_voxel_net or vp_megvii:
             raise NotImplementedError("options unused by projects/configs/.../stereoscene.py are not built")
@@ -527,6 +530,7 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
         self.stereo_volume_net = GwcNet_volume_encoder(self.D, 32, warp_align_corners)
         self.volume_interaction = volume_interaction()
         self.cam_depth_range = grid_config["dbound"]
+        self.constant_std = 0.5                       # VT:298: the only value the reference can run with (see get_klv_depth_loss)
 
     # geometry -------------------------------------------------------------------------------
     def create_frustum(self):
@@ -668,8 +672,20 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
         g = torch.where((g < self.D + 1) & (g >= 0.0), g, torch.zeros_like(g))
         return vals, TF.one_hot(g.long(), num_classes=self.D + 1)[:, 1:].float()
 
+    def get_klv_depth_loss(self, depth_labels, depth_preds):
+        """Gaussian KL depth loss (VT:390-403 + utils/gaussian.py:90-130), already multiplied by ``loss_depth_weight``: the
+        target of a feature pixel is N(m / dd, constant_std / dd) integrated over the bin edges, m = its nearest LiDAR depth.
+        ``depth_kld_units="reference"`` evaluates the cdf at the edges in METRES as the reference executes it (the mean is in bin
+        units, so the target peaks at the bin that holds 2 m metres for dd = 0.5); "bins" evaluates it at edges / dd.  Only the
+        constant standard deviation is built: the reference's patch-statistics branch (constant_std=None) raises on any block
+        without a return.  No foreground pixel gives 0 with a zero gradient (the reference: NaN)."""
+        return F.depth_kld_loss(depth_labels, depth_preds, self.downsample, self.cam_depth_range, self.loss_depth_weight,
+                                self.constant_std, self.depth_kld_units)
+
     def get_depth_loss(self, depth_labels, depth_preds):
-        """BCE depth loss (VT:375-388,405-416)."""
+        """Depth loss (VT:375-416): ``loss_depth_type`` "bce" (below) or "kld" (get_klv_depth_loss)."""
+        if self.loss_depth_type == "kld":
+            return self.get_klv_depth_loss(depth_labels, depth_preds)
         if self.loss_depth_type != "bce":
             raise NotImplementedError(self.loss_depth_type)
         if (F.DEPTH_BCE and depth_preds.is_cuda and depth_preds.dtype == torch.float32 and depth_labels.dtype == torch.float32

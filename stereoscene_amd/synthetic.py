@@ -72,6 +72,45 @@ def lovasz_case(name):
     return logits, lab
 
 
+# Cases of the Gaussian KL depth-loss tests (tools/make_golden_depth_kld.py records the reference on them): name -> (gt_depths
+# shape [B, N, H, W], ds, dbound, units, density of LiDAR returns, their value range).  A: the reference grid (D = 112), 30 feature
+# pixels, blocks with 0 / 1 / many returns and the planted edge depths of DEPTH_KLD_PLANTS; B: D = 13 (no multiple of the
+# kernel's chunk count), 552 pixels = three thread blocks with a ragged last one, ds = 4, returns on both sides of the range;
+# C: B without any return; D: B in bin units; E: the kitti_d192 depth range (D = 192) on a 2 x 3 feature map.
+DEPTH_KLD_CASES = {"A": ((1, 2, 48, 80), 16, (2.0, 58.0, 0.5), "reference", 0.004, (2.2, 28.0)),
+                   "B": ((2, 1, 48, 92), 4, (2.0, 8.5, 0.5), "reference", 0.08, (1.5, 9.5)),
+                   "C": ((2, 1, 48, 92), 4, (2.0, 8.5, 0.5), "reference", 0.0, (1.5, 9.5)),
+                   "D": ((2, 1, 48, 92), 4, (2.0, 8.5, 0.5), "bins", 0.08, (1.5, 9.5)),
+                   "E": ((1, 1, 16, 24), 8, (2.0, 98.0, 0.5), "reference", 0.03, (1.0, 60.0))}
+# Case A, camera 0, feature row 0: feature column -> ((row, column) inside the 16 x 16 block, depth), the rest of the block empty.
+# d0 exactly (foreground); d1 - dd exactly (foreground); the next fp32 above it (background); 1.9 next to a deeper return (the
+# minimum decides: background); 33.6 (foreground, its Gaussian is centred at bin 67.2 = 33.6 / dd, beyond the last edge 57.75: an
+# all-zero target row that still counts in the divisor).
+DEPTH_KLD_PLANTS = {0: (((3, 7), 2.0),), 1: (((15, 15), 57.5),), 2: (((0, 0), float(np.nextafter(np.float32(57.5), np.float32(100.0)))),),
+                    3: (((8, 1), 1.9), ((2, 12), 7.0)), 4: (((11, 4), 33.6),)}
+
+
+def depth_kld_case(name):
+    """(gt_depths fp32 [B,N,H,W], depth_pred fp32 [B*N,D,H/ds,W/ds] with rows that sum to 1, ds, dbound, units) of
+    DEPTH_KLD_CASES[name]."""
+    shape, ds, dbound, units, density, (lo, hi) = DEPTH_KLD_CASES[name]
+    assert name != "E" or list(dbound) == grid_config(CFG_K192)["dbound"]
+    src = "B" if name in "CD" else name
+    u = hash_uniform(f"depth_kld_{src}/mask", shape, 0.0, 1.0)
+    d = hash_uniform(f"depth_kld_{src}/val", shape, lo, hi)
+    gt = torch.where(u < density, d, torch.zeros_like(d))
+    if name == "A":
+        for col, plants in DEPTH_KLD_PLANTS.items():
+            gt[0, 0, :ds, col * ds:(col + 1) * ds] = 0.0
+            for (i, j), v in plants:
+                gt[0, 0, i, col * ds + j] = v
+    B, N, H, W = shape
+    D = int(round((dbound[1] - dbound[0]) / dbound[2]))
+    w = hash_uniform(f"depth_kld_{src}/pred", (B * N, D, H // ds, W // ds), 0.02, 1.0).double()
+    w = w * w * w                                    # products and one division in float64, rounded once: exactly reproducible
+    return gt, (w / w.sum(dim=1, keepdim=True)).float(), ds, dbound, units
+
+
 _NORM_TOKENS = (".bn", ".gn", "norm")
 
 
