@@ -482,6 +482,33 @@ int ssbev_lovasz_bwd(const float* logits, const uint8_t* label, const float* dj,
                      const float* grad_out, float* grad_logits, const ssbev_lovasz_dims* d, void* ws, size_t ws_bytes,
                      ssbev_stream_t stream);
 
+/* OHEM cross-entropy voxel loss (since version 110): OHEM_CE_ssc_loss(up(logits), label, class_weight, top_k) of the reference
+ * (utils/semkitti.py:151-185): l_v = w[t_v] * CE_v per labelled voxel; per sample the k_b = int(M_b * top_k) largest of its M_b
+ * losses are kept; loss = sum(kept l) / max(sum of w[t] over the kept voxels, 1e-4), both sums over the batch.  No sort: the
+ * losses are >= +0, so their fp32 bit patterns order like unsigned integers and a most-significant-digit-first radix select
+ * finds the k_b-th largest exactly in four 8-bit histogram passes.  The up-sampled logits are never written.
+ *   dims          ssbev_lovasz_dims' fields (B, D, H, W: the LOGITS' grid; C == 20; ignore; upsample 0 / 1) + top_k in (0, 1]
+ *   logits        [B, D, H, W, 20] channels-last fp32;  label [B, D', H', W'] uint8 (a value >= 20 counts as ignored)
+ *   class_weight  [20] float (device)
+ *   loss          one float (device); 0 when no voxel is labelled or every k_b is 0
+ *   mask          [B D' H' W'] one byte per voxel (device), kept by the caller for backward: 1 = in the selection
+ *   inv_wsum      one float (device), kept for backward: 1 / max(sum of w[t] over the selection, 1e-4)
+ *   backward      grad_logits [B, D, H, W, 20] = grad_out[0] * d loss / d logits (grad_out: one float on the device); the
+ *                 divisor carries no gradient, as in the reference
+ * k_b = (long long)((double)M_b * top_k) is computed on the device; nothing is read back to the host.  Losses equal to the
+ * threshold are taken lowest flat voxel index first; integer atomics and fixed-order double sums only: every run gives the
+ * same bits.  After ssbev_ohem_ce_fwd the first B D' H' W' words of ws hold the per-voxel losses as fp32 (0xFFFFFFFF for an
+ * ignored voxel).  SSBEV_EINVAL before any device work: NULL pointers, non-positive dims, C != 20, upsample not 0 / 1, top_k
+ * outside (0, 1], 20 x voxels >= 2^31;  SSBEV_EWORKSPACE: ws_bytes below the query.  The queries answer 0 for refused dims. */
+typedef struct { int B, D, H, W, C, ignore, upsample; double top_k; } ssbev_ohem_dims;
+size_t ssbev_ohem_ce_workspace(const ssbev_ohem_dims* d);
+int ssbev_ohem_ce_fwd(const float* logits, const uint8_t* label, const float* class_weight, float* loss, uint8_t* mask,
+                      float* inv_wsum, const ssbev_ohem_dims* d, void* ws, size_t ws_bytes, ssbev_stream_t stream);
+size_t ssbev_ohem_ce_bwd_workspace(const ssbev_ohem_dims* d);
+int ssbev_ohem_ce_bwd(const float* logits, const uint8_t* label, const float* class_weight, const uint8_t* mask,
+                      const float* inv_wsum, const float* grad_out, float* grad_logits, const ssbev_ohem_dims* d, void* ws,
+                      size_t ws_bytes, ssbev_stream_t stream);
+
 /* Running statistics of a training-mode BatchNorm from the (mean, rstd) ssbev_groupnorm_fwd returned with G == C over the
  * batch: running_mean <- (1-m) running_mean + m mean; running_var <- (1-m) running_var + m var n/(n-1)
  * (torch.nn.BatchNorm3d as built at ViewTransformerLSSVoxel.py:83-88; n = elements per channel). */

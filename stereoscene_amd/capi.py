@@ -90,6 +90,10 @@ class LovaszDims(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("B", "D", "H", "W", "C", "ignore", "upsample")]
 
 
+class OhemDims(C.Structure):
+    _fields_ = LovaszDims._fields_ + [("top_k", C.c_double)]
+
+
 class GemmDims(C.Structure):
     _fields_ = [("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("batch", C.c_int),
                 ("lda", C.c_int64), ("ldb", C.c_int64), ("ldc", C.c_int64), ("sa", C.c_int64), ("sb", C.c_int64), ("sc", C.c_int64),
@@ -296,6 +300,10 @@ SIGNATURES = {
     "ssbev_lovasz_fwd": (C.c_int, [_P] * 5 + [C.POINTER(LovaszDims), _P, C.c_size_t, _P]),
     "ssbev_lovasz_bwd_workspace": (C.c_size_t, [C.POINTER(LovaszDims)]),
     "ssbev_lovasz_bwd": (C.c_int, [_P] * 6 + [C.POINTER(LovaszDims), _P, C.c_size_t, _P]),
+    "ssbev_ohem_ce_workspace": (C.c_size_t, [C.POINTER(OhemDims)]),
+    "ssbev_ohem_ce_fwd": (C.c_int, [_P] * 6 + [C.POINTER(OhemDims), _P, C.c_size_t, _P]),
+    "ssbev_ohem_ce_bwd_workspace": (C.c_size_t, [C.POINTER(OhemDims)]),
+    "ssbev_ohem_ce_bwd": (C.c_int, [_P] * 7 + [C.POINTER(OhemDims), _P, C.c_size_t, _P]),
     "ssbev_grad_norm_workspace": (C.c_size_t, []),
     "ssbev_grad_norm": (C.c_int, [_P, C.c_int64, _P, _P, C.c_size_t, _P]),
     "ssbev_adamw_step": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.POINTER(AdamWCfg), _P, _P]),

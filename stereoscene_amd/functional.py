@@ -2337,6 +2337,93 @@ def lovasz_softmax(logits, label_u8, ignore=255):
     return losses.lovasz_softmax_loss(logits, label_u8, ignore).float()
 
 
+OHEM = os.environ.get("SSBEV_OHEM", "1") != "0"              # fused OHEM cross entropy (0 = the tensor form: CE volume + one stable sort per sample)
+
+
+def ohem_supported(logits, label):
+    """The fused OHEM cross entropy serves what the fused Lovasz-softmax serves: fp32 20-class logits on the GPU that sit on the
+    label grid or at exactly half of it."""
+    return lovasz_supported(logits, label)
+
+
+def _ohem_forward(logits, label_u8, class_weight, top_k):
+    """``ssbev_ohem_ce_fwd``: (loss [1], mask uint8 [voxels], inv_wsum [1], channels-last logits, labels, weights, dims, ws)."""
+    lib = capi.load()
+    xcl = to_cl(_f32(logits, "ohem_ce_loss"))
+    B, D, H, W, Cch = xcl.shape
+    lab = label_u8.contiguous()
+    up = int(tuple(lab.shape[1:]) != (D, H, W))
+    top_k = float(top_k)
+    if not 0.0 < top_k <= 1.0:
+        raise capi.SsbevError(f"ohem_ce_loss: top_k must be in (0, 1], got {top_k}")
+    d = capi.OhemDims(B, D, H, W, Cch, 255, up, top_k)
+    dev = logits.device
+    cw = class_weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if cw.numel() != Cch:
+        raise capi.SsbevError(f"ohem_ce_loss: {Cch} class weights expected, got {cw.numel()}")
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    inv = torch.empty(1, dtype=torch.float32, device=dev)
+    mask = torch.empty(lab.numel(), dtype=torch.uint8, device=dev)
+    ws = _ws(lib.ssbev_ohem_ce_workspace(C.byref(d)), dev)
+    # the loss pass reads the logits' taps and writes 4 B per voxel; three histogram passes, the tie count and the selection read them
+    with _span("ohem", 0.0, 4.0 * xcl.numel() + 3.0 * lab.numel() + 4.0 * 6 * lab.numel(), "fwd   ohem"):
+        capi.check(lib.ssbev_ohem_ce_fwd(capi.ptr(xcl), capi.ptr(lab), capi.ptr(cw), capi.ptr(loss), capi.ptr(mask), capi.ptr(inv),
+                                         C.byref(d), capi.ptr(ws), ws.numel(), capi.stream()), "ssbev_ohem_ce_fwd")
+    return loss, mask, inv, xcl, lab, cw, d, ws
+
+
+def ohem_voxel_losses(logits, label_u8, class_weight, top_k=0.25):
+    """Diagnostics: (per-voxel fp32 losses of the fused path, NaN where ignored, in the labels' shape; the selection mask) -- a
+    read of the head of the forward workspace, for the accuracy tests and tools/ohem_probe.py."""
+    label_u8 = label_u8.to(torch.uint8)
+    _, mask, _, _, lab, _, _, ws = _ohem_forward(logits, label_u8, class_weight, top_k)
+    bits = ws[:4 * lab.numel()].clone().view(torch.int32)
+    l = torch.where(bits == -1, torch.full_like(bits, 0x7FC00000), bits).view(torch.float32)
+    return l.view(lab.shape), mask.view(lab.shape).bool()
+
+
+class _OhemCe(torch.autograd.Function):
+    """logits [B,20,D,H,W], label uint8 [B,D',H',W'] (the same grid or exactly twice it), class weights [20] -> the OHEM cross
+    entropy (0-dim fp32), ``ssbev_ohem_ce_fwd / _bwd``.  Forward keeps one byte per voxel (the selection) and the reciprocal of
+    the clamped weight sum on the device; nothing is read back.  No gradient for the class weights (a buffer of the head)."""
+
+    @staticmethod
+    def forward(ctx, logits, label_u8, class_weight, top_k):
+        loss, mask, inv, xcl, lab, cw, d, _ = _ohem_forward(logits, label_u8, class_weight, top_k)
+        ctx.save_for_backward(xcl, lab, cw, mask, inv)
+        ctx.dims = d
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = capi.load()
+        xcl, lab, cw, mask, inv = ctx.saved_tensors
+        d = ctx.dims
+        gl = g.to(torch.float32).reshape(1).contiguous()
+        gx = torch.empty_like(xcl)
+        ws = _ws(lib.ssbev_ohem_ce_bwd_workspace(C.byref(d)), xcl.device)
+        with _span("ohem", 0.0, 8.0 * xcl.numel() + 2.0 * lab.numel() + 8.0 * 20 * lab.numel() * d.upsample, "bwd   ohem"):
+            capi.check(lib.ssbev_ohem_ce_bwd(capi.ptr(xcl), capi.ptr(lab), capi.ptr(cw), capi.ptr(mask), capi.ptr(inv), capi.ptr(gl),
+                                             capi.ptr(gx), C.byref(d), capi.ptr(ws), ws.numel(), capi.stream()),
+                       "ssbev_ohem_ce_bwd")
+        return from_cl(gx), None, None, None
+
+
+def ohem_ce_loss(logits, label_u8, class_weight, top_k=0.25):
+    """OHEM cross entropy of ``up(logits)`` against ``label_u8`` (255 = ignore): per sample the ``int(M_b * top_k)`` largest
+    class-weighted voxel losses, their sum over the sum of their class weights (clamped at 1e-4) over the batch; 0 with a zero
+    gradient when nothing is selected; fp32, 0-dim.  Supported inputs (``ohem_supported``) with ``OHEM`` on run on the fused HIP
+    path; anything else on the tensor form of plugin/losses.py after ``upsample_trilinear``."""
+    label_u8 = label_u8.to(torch.uint8)
+    if OHEM and ohem_supported(logits, label_u8):
+        return _OhemCe.apply(logits, label_u8, class_weight, float(top_k))
+    from .plugin import losses
+    if not OHEM and logits.is_cuda:
+        up = upsample_trilinear(logits, label_u8.shape[-3:])
+        return losses.ohem_ce_tensor(up, label_u8, class_weight.to(up), top_k).float()
+    return losses.ohem_ce_loss(logits, label_u8, class_weight, top_k).float()
+
+
 DEPTH_BCE = os.environ.get("SSBEV_DEPTH_BCE", "1") != "0"    # fused depth loss (0 = the ~35 ATen ops of the tensor expression)
 
 

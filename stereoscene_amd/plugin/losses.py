@@ -152,8 +152,51 @@ def lovasz_softmax_loss(logits, gt_occ, ignore=255):
     return lovasz_softmax_tensor(logits, gt_occ, ignore)
 
 
+def ohem_k(n_labelled, top_k):
+    """Voxels a sample keeps: the reference's ``int(flatten_loss_i.shape[0] * top_k)`` (a double product, truncated)."""
+    return int(n_labelled * top_k)
+
+
+def ohem_ce_tensor(logits, target, class_weights, top_k=0.25):
+    """OHEM_CE_ssc_loss (utils/semkitti.py:151-185) of logits that already sit on the label grid, from tensor ops on any device
+    and in the logits' dtype: class-weighted cross entropy per voxel; per sample the ``int(M_b * top_k)`` largest losses of its
+    M_b labelled voxels; sum of the kept losses over the sum of the kept voxels' class weights (clamped at 1e-4), both over the
+    batch.  The selection is a STABLE descending sort, so equal losses go to the lowest voxel index -- the rule of the fused
+    kernel (``torch.topk`` leaves the choice among ties open).  The losses are canonicalised to +0.0 first (a saturated voxel
+    gives -0.0).  A zero with a zero gradient when nothing is selected."""
+    loss = TF.cross_entropy(logits, target.long(), weight=class_weights, ignore_index=255, reduction="none").flatten(1)
+    loss = loss + 0.0                                                 # -0.0 -> +0.0
+    flat = target.flatten(1)
+    top, norm = logits.sum() * 0.0, class_weights.sum() * 0.0
+    for b in range(loss.shape[0]):
+        valid = flat[b] != 255
+        li = loss[b, valid]
+        k = ohem_k(li.shape[0], top_k)
+        if k == 0:
+            continue
+        keep = torch.argsort(li.detach(), descending=True, stable=True)[:k]
+        top = top + li[keep].sum()
+        norm = norm + class_weights[flat[b, valid].long()][keep].sum()
+    return top / torch.clamp_min(norm.detach(), 1e-4)
+
+
+def ohem_ce_loss(logits, gt_occ, class_weights, top_k=0.25):
+    """OHEM cross-entropy voxel loss of the head (occhead.py:315-319): logits [B,C,d,h,w] are up-sampled trilinearly to the grid
+    of ``gt_occ`` [B,D,H,W].  The fused HIP path serves what ``functional.ohem_supported`` accepts; everything else (other
+    devices, dtypes, class counts or ratios, ``SSBEV_OHEM=0``) runs ``ohem_ce_tensor``."""
+    from .. import functional as F
+    if F.OHEM and F.ohem_supported(logits, gt_occ):
+        return F.ohem_ce_loss(logits, gt_occ, class_weights, top_k)
+    if logits.shape[-3:] != gt_occ.shape[-3:]:
+        if logits.is_cuda:
+            logits = F.upsample_trilinear(logits, gt_occ.shape[-3:])
+        else:                                                         # (the HIP up-sampling has no CPU form)
+            logits = TF.interpolate(logits, size=tuple(gt_occ.shape[-3:]), mode="trilinear", align_corners=False)
+    return ohem_ce_tensor(logits, gt_occ, class_weights.to(logits), top_k)
+
+
 def occ_losses_fused(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0, w_geo=1.0, compute_metric=False,
-                     w_lovasz=0.0):
+                     w_lovasz=0.0, w_ohem=0.0, ohem_topk=0.25):
     """Same losses / metric as ``occ_losses`` from the sums of the fused HIP epilogue (one pass over the coarse
     logits; the up-sampled logits, probabilities and one-hot volumes are never materialised)."""
     from .. import functional as F
@@ -170,6 +213,8 @@ def occ_losses_fused(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0
             out[f"loss_voxel_sem_scal_{tag}"] = sem
         if w_geo > 0:
             out[f"loss_voxel_geo_scal_{tag}"] = geo
+        if w_ohem > 0:
+            out[f"loss_voxel_sem_ohem_{tag}"] = ohem_ce_loss(logits, gt_occ, class_weights, ohem_topk) * w_ohem
         if w_lovasz > 0:
             out[f"loss_voxel_lovasz_{tag}"] = lovasz_softmax_loss(logits, gt_occ) * w_lovasz
         if compute_metric:
@@ -194,6 +239,8 @@ def occ_losses_fused(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0
         inter = occ_t - (sum_p[0] - nom[0])
         geo = _nll1(inter / (M - sum_p[0])) + _nll1(inter / occ_t) + _nll1(nom[0] / cnt[0])
         out[f"loss_voxel_geo_scal_{tag}"] = geo.float() * w_geo
+    if w_ohem > 0:
+        out[f"loss_voxel_sem_ohem_{tag}"] = ohem_ce_loss(logits, gt_occ, class_weights, ohem_topk) * w_ohem
     if w_lovasz > 0:
         out[f"loss_voxel_lovasz_{tag}"] = lovasz_softmax_loss(logits, gt_occ) * w_lovasz
     if compute_metric:
@@ -209,10 +256,12 @@ def occ_losses_fused(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0
     return out
 
 
-def occ_losses(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0, w_geo=1.0, compute_metric=False, w_lovasz=0.0):
-    """occhead.py:291-361: trilinear upsample to the label grid, CE + sem_scal + geo_scal (+ Lovasz-softmax, + metric)."""
+def occ_losses(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0, w_geo=1.0, compute_metric=False, w_lovasz=0.0,
+               w_ohem=0.0, ohem_topk=0.25):
+    """occhead.py:291-361: trilinear upsample to the label grid, CE + sem_scal + geo_scal (+ OHEM CE, + Lovasz-softmax, + metric)."""
     if (logits.is_cuda and logits.shape[1] == 20 and all(o == 2 * i for o, i in zip(gt_occ.shape[-3:], logits.shape[-3:]))):
-        return occ_losses_fused(logits, gt_occ, class_weights, tag, w_ce, w_sem, w_geo, compute_metric, w_lovasz)
+        return occ_losses_fused(logits, gt_occ, class_weights, tag, w_ce, w_sem, w_geo, compute_metric, w_lovasz, w_ohem,
+                                ohem_topk)
     if logits.shape[-3:] != gt_occ.shape[-3:]:
         from ..functional import upsample_trilinear
         logits = upsample_trilinear(logits, gt_occ.shape[-3:])
@@ -226,6 +275,8 @@ def occ_losses(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0, w_ge
             out[f"loss_voxel_sem_scal_{tag}"] = sem * w_sem
         if w_geo > 0:
             out[f"loss_voxel_geo_scal_{tag}"] = geo * w_geo
+    if w_ohem > 0:
+        out[f"loss_voxel_sem_ohem_{tag}"] = ohem_ce_loss(logits, gt_occ, class_weights, ohem_topk) * w_ohem
     if w_lovasz > 0:
         out[f"loss_voxel_lovasz_{tag}"] = lovasz_softmax_loss(logits, gt_occ) * w_lovasz
     if compute_metric:

@@ -147,9 +147,16 @@ class OccHead(nn.Module):
         # a stream synchronisation right before the losses) without adding a state-dict key the reference does not have
         self.register_buffer("class_weights", L.semkitti_class_weights(), persistent=False)
         self.semkitti_loss_weight_cfg = semkitti_loss_weight_cfg or {}
-        for k in ("voxel_ohem", "frustum_dist", "voxel_dice", "voxel_lga"):
+        for k in ("frustum_dist", "voxel_dice", "voxel_lga"):
             if self.semkitti_loss_weight_cfg.get(k, 0.0) > 0:
                 raise NotImplementedError(f"loss '{k}' is disabled in the reference config and not built")
+        # the OHEM cross entropy runs behind the reference's constructor flag: the weight alone does not switch it on
+        self.use_ohem_loss, self.ohem_topk = bool(use_ohem_loss), float(ohem_topk)
+        if not 0.0 < self.ohem_topk <= 1.0:
+            raise ValueError(f"ohem_topk must be in (0, 1], got {ohem_topk}")
+        if self.semkitti_loss_weight_cfg.get("voxel_ohem", 0.0) > 0 and not self.use_ohem_loss:
+            raise NotImplementedError("loss 'voxel_ohem' is disabled in the reference config: pass use_ohem_loss=True to "
+                                      "OccHead to compute it")
 
     def forward_voxel(self, voxel_feats):
         return [conv(f) for f, conv in zip(voxel_feats, self.occ_convs)]
@@ -162,7 +169,8 @@ class OccHead(nn.Module):
         w = self.semkitti_loss_weight_cfg
         return L.occ_losses(output_voxels, target_voxels, self.class_weights.to(output_voxels), tag,
                             w.get("voxel_ce", 0.0), w.get("voxel_sem_scal", 0.0), w.get("voxel_geo_scal", 0.0),
-                            compute_metric, w.get("voxel_lovasz", 0.0))
+                            compute_metric, w.get("voxel_lovasz", 0.0),
+                            w.get("voxel_ohem", 0.0) if self.use_ohem_loss else 0.0, self.ohem_topk)
 
     def loss(self, output_voxels=None, target_voxels=None, output_points=None, target_points=None, img_metas=None,
              **kwargs):

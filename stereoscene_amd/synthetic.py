@@ -72,6 +72,39 @@ def lovasz_case(name):
     return logits, lab
 
 
+# Cases of the OHEM cross-entropy tests (tools/make_golden_ohem.py records the reference on them): name -> (logits shape, label
+# grid, top_k).  The labels are the Lovasz cases' (A: two samples with different M_b and k_b; B: 14 716 labelled voxels = many
+# tiles; C: A's labels with the logits on the label grid; D: all-zero logits, every loss is w_t * log 20 and the threshold falls
+# inside one class's tie group; E: nothing labelled; F: two labelled voxels, k = 0; G: fewer voxels than a wave); H is C with +40
+# on the target logit of a hashed ~20 % of the voxels: exactly zero fp32 losses inside the selection.
+OHEM_CASES = {"A": ((2, 20, 8, 6, 4), (2, 16, 12, 8), 0.25), "B": ((1, 20, 16, 16, 8), (1, 32, 32, 16), 0.25),
+              "C": ((2, 20, 16, 12, 8), (2, 16, 12, 8), 0.9), "D": ((2, 20, 8, 6, 4), (2, 16, 12, 8), 0.25),
+              "E": ((2, 20, 8, 6, 4), (2, 16, 12, 8), 0.25), "F": ((2, 20, 8, 6, 4), (2, 16, 12, 8), 0.25),
+              "G": ((1, 20, 3, 2, 2), (1, 6, 4, 4), 0.25), "H": ((2, 20, 16, 12, 8), (2, 16, 12, 8), 0.9)}
+# 0: the Lovasz case's tensors; bumped (logits "ohem_<case><seed>_x"; for A also the labels, which C D F H share) when a sample's
+# float64 gap between the k-th and the (k+1)-th loss is below 64 x the largest fp32 per-voxel loss error, or when A's two samples
+# would keep the same number of voxels (the generator refuses the fixture)
+OHEM_SEED = {"A": 1, "B": 1, "C": 0, "G": 0}
+
+
+def ohem_case(name):
+    """(logits fp32 [B,20,d,h,w] ~ N(0, 2^2), labels uint8 [B,D,H,W], top_k) of OHEM_CASES[name]."""
+    coarse, fine, top_k = OHEM_CASES[name]
+    src = {"D": "A", "E": "A", "F": "A", "H": "C"}.get(name, name)
+    _, lab = lovasz_case("C" if name == "H" else name)
+    if name in "ACDH" and OHEM_SEED["A"]:
+        lab = lovasz_labels(f"ohem_A{OHEM_SEED['A']}", fine)
+    seed = OHEM_SEED[src]
+    logits = hash_normal(f"ohem_{src}{seed}_x" if seed else f"lovasz_{src}{LOVASZ_SEED[src]}_x", coarse, 2.0)
+    if name == "D":
+        logits = torch.zeros(coarse)
+    if name == "H":
+        plant = (hash_uniform("ohem_H_plant", fine, 0.0, 1.0) < 0.2) & (lab != 255)
+        t = lab.long().clamp(max=19).unsqueeze(1)
+        logits = logits + 40.0 * torch.zeros_like(logits).scatter_(1, t, plant.unsqueeze(1).float())
+    return logits, lab, top_k
+
+
 # Cases of the Gaussian KL depth-loss tests (tools/make_golden_depth_kld.py records the reference on them): name -> (gt_depths
 # shape [B, N, H, W], ds, dbound, units, density of LiDAR returns, their value range).  A: the reference grid (D = 112), 30 feature
 # pixels, blocks with 0 / 1 / many returns and the planted edge depths of DEPTH_KLD_PLANTS; B: D = 13 (no multiple of the
