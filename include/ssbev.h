@@ -672,12 +672,22 @@ int ssbev_chan_scale(const float* x, const float* gate, float* y, int B, int64_t
  *   output_adjoint:    gy [B,D,H,W,C] -> Z [64][T][C]   (A gy A^T, weight gradient)
  * Replaces nn.Conv3d at resnet3d.py:18-32, second_fpn_3d.py:53-69 (3x3x3 convs), occhead.py:100-107.
  * ------------------------------------------------------------------------------------------ */
-typedef struct { int B, D, H, W, C; } ssbev_wino_dims;
+typedef struct { int B, D, H, W, C; int dil; } ssbev_wino_dims;   /* dil: 0 / 1 = undilated; > 1: see ssbev_wino2d_* below */
 int ssbev_wino_input_transform(const float* x, float* V, const ssbev_wino_dims* d, ssbev_stream_t stream);
 int ssbev_wino_output_transform(const float* M, float* y, const ssbev_wino_dims* d, ssbev_stream_t stream);
 int ssbev_wino_output_adjoint(const float* gy, float* Z, const ssbev_wino_dims* d, ssbev_stream_t stream);
 /* 2-D variant F(2x2, 3x3) for the 3x3 conv2d layers of DepthNet (ViewTransformerLSSBEVDepth.py:461-504): 16 frequencies,
- * T = B * D * H/2 * W/2 (D is a batch axis), buffers [16][T][C]. */
+ * T = B * D * H/2 * W/2 (D is a batch axis), buffers [16][T][C].
+ * ssbev_wino_dims.dil > 1 (these three fp32 functions and ssbev_wino2d_output_transform_acc only; every other ssbev_wino*
+ * function answers SSBEV_EINVAL): the 3x3 layer with dilation = padding = dil.  Every residue class modulo dil is tiled on
+ * its own with its rows / columns dil apart, so H and W may be odd and nothing is padded or copied: T = B * D * TH * TW with
+ * TH = ssbev_wino2d_axis_tiles(H, dil, ...), TW likewise (each at most SSBEV_WINO2D_MAX_AXIS_TILES, H and W at most 65535).
+ * Weight functions and frequency products are those of the undilated layer. */
+#define SSBEV_WINO2D_MAX_AXIS_TILES 128
+/* Host only: tiles along an axis of `extent` positions = sum over ph < min(dil, extent) of ceil(ceil((extent - ph) / dil) / 2),
+ * numbered phase-major; first[i] (i < cap; first may be NULL) = first output coordinate ph + 2 t dil of tile i, whose second
+ * output is dil further (outside the axis for the half-empty last tile of a class).  0 for extent or dil <= 0. */
+int ssbev_wino2d_axis_tiles(int extent, int dil, uint16_t* first, int cap);
 int ssbev_wino2d_input_transform(const float* x, float* V, const ssbev_wino_dims* d, ssbev_stream_t stream);
 int ssbev_wino2d_output_transform(const float* M, float* y, const ssbev_wino_dims* d, ssbev_stream_t stream);
 int ssbev_wino2d_output_adjoint(const float* gy, float* Z, const ssbev_wino_dims* d, ssbev_stream_t stream);

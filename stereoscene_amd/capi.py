@@ -79,7 +79,7 @@ class DwDims(C.Structure):
 
 
 class WinoDims(C.Structure):
-    _fields_ = [(n, C.c_int) for n in ("B", "D", "H", "W", "C")]
+    _fields_ = [(n, C.c_int) for n in ("B", "D", "H", "W", "C", "dil")]      # dil: 0 / 1 undilated; > 1 the 2-D F(2,3) transforms only
 
 
 class UpsampleDims(C.Structure):
@@ -244,6 +244,7 @@ SIGNATURES = {
     "ssbev_wino43_df_wgrad_workspace": (C.c_size_t, [C.POINTER(WinoDims), C.c_int]),
     "ssbev_wino43_df_wgrad": (C.c_int, [_P, _P, _P, C.POINTER(WinoDims), C.c_int, _P, C.c_size_t, _P]),
     "ssbev_wino43_df_plan_query": (C.c_int, [C.POINTER(WinoDims), C.c_int, C.POINTER(Wino43DfPlan)]),
+    "ssbev_wino2d_axis_tiles": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_uint16), C.c_int]),
     "ssbev_wino2d_input_transform": (C.c_int, [_P, _P, C.POINTER(WinoDims), _P]),
     "ssbev_wino2d_output_transform": (C.c_int, [_P, _P, C.POINTER(WinoDims), _P]),
     "ssbev_wino2d_output_adjoint": (C.c_int, [_P, _P, C.POINTER(WinoDims), _P]),

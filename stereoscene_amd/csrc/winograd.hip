@@ -15,7 +15,23 @@
 
 namespace {
 
-struct WinoGeom { int B, D, H, W, C; int acc = 0; };     // acc: the output transforms ADD to y (gradient slots, functional.fork)
+struct WinoGeom {                                          // acc: the output transforms ADD to y (gradient slots, functional.fork)
+  int B, D, H, W, C; int acc = 0;
+  static constexpr bool kDil = false;
+};
+// Dilated 2-D tiling (3x3, dilation = padding = dil > 1).  Such a convolution only couples positions of the same residue class
+// modulo dil, so every class (ph, pw) is tiled on its own: tile (th, tw) of the class owns the outputs (ph + (2 th + j) dil,
+// pw + (2 tw + k) dil), j, k = 0..1, and reads the inputs (ph + (2 th + i - 1) dil, ...), i = 0..3 -- the undilated tile with
+// every step multiplied by dil.  Reads outside the map are zeros (the convolution's own padding and the empty half of a class'
+// last tile), stores outside it are dropped.  A class of n = ceil((H - ph) / dil) rows takes ceil(n / 2) tile rows; classes
+// ph >= H have none; tile rows per map TH = sum over ph of ceil(n_ph / 2), numbered phase-major (columns alike).  h0 / w0: first
+// output row / column of every tile row / column, filled by the host (wino2d_axis_table); frequency buffers [16][B D TH TW][C].
+constexpr int kWinoMaxAxisTiles = SSBEV_WINO2D_MAX_AXIS_TILES;
+struct WinoGeomDil : WinoGeom {
+  int dil, TH, TW;
+  unsigned short h0[kWinoMaxAxisTiles], w0[kWinoMaxAxisTiles];
+  static constexpr bool kDil = true;
+};
 __device__ const float kWinoZeros[4] = {0.f, 0.f, 0.f, 0.f};
 
 // Storage type of the transformed-domain tensors (V, M, Z): float, or bf16 bit patterns (the `_bf16` entry points: half
@@ -84,6 +100,25 @@ __device__ __forceinline__ void wino_decode2(long i, const WinoGeom& g, int& c, 
   tw = (int)(t % (g.W / 2)); t /= g.W / 2;
   th = (int)(t % (g.H / 2));
   bd = t / (g.H / 2);
+}
+
+// ... and for the 2-D transforms: (h0, w0) = first output position of the tile, dl = step between its rows / columns
+template <int NV>
+__device__ __forceinline__ void wino_tile2(long i, const WinoGeom& g, int& c, long& tile, int& h0, int& w0, int& dl, long& bd) {
+  int tw, th;
+  wino_decode2<NV>(i, g, c, tile, tw, th, bd);
+  h0 = 2 * th; w0 = 2 * tw; dl = 1;
+}
+template <int NV>
+__device__ __forceinline__ void wino_tile2(long i, const WinoGeomDil& g, int& c, long& tile, int& h0, int& w0, int& dl, long& bd) {
+  const int cq = g.C / NV;
+  c = NV * (int)(i % cq);
+  long t = i / cq;
+  tile = t;
+  w0 = g.w0[(int)(t % g.TW)]; t /= g.TW;
+  h0 = g.h0[(int)(t % g.TH)];
+  bd = t / g.TH;
+  dl = g.dil;
 }
 
 template <typename TF, typename TA = float, int NV = 1>
@@ -239,21 +274,21 @@ wino_output_adjoint_kernel(const TA* __restrict__ gy, TF* __restrict__ Z, WinoGe
 }
 
 // ---- 2-D variant, F(2x2, 3x3): 16 frequencies, tiles over (h, w); the D axis of the dims struct is a batch axis ----
-template <typename TF, typename TA = float, int NV = 1>
+template <typename TF, typename TA = float, int NV = 1, typename G = WinoGeom>
 __global__ void __launch_bounds__(256)
-wino2d_input_kernel(const TA* __restrict__ x, TF* __restrict__ V, WinoGeom g, long total) {
+wino2d_input_kernel(const TA* __restrict__ x, TF* __restrict__ V, G g, long total) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
-  int c, tw, th;
+  int c, h0, w0, dl;
   long tile, bd;
-  wino_decode2<NV>(i, g, c, tile, tw, th, bd);
+  wino_tile2<NV>(i, g, c, tile, h0, w0, dl, bd);
   float v[NV][16];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    const int h = 2 * th - 1 + e;
+    const int h = h0 + (e - 1) * dl;
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
-      const int w = 2 * tw - 1 + f;
+      const int w = w0 + (f - 1) * dl;
       const bool ok = h >= 0 && h < g.H && w >= 0 && w < g.W;
       float t[NV];
 #pragma unroll
@@ -280,14 +315,17 @@ wino2d_input_kernel(const TA* __restrict__ x, TF* __restrict__ V, WinoGeom g, lo
   }
 }
 
-template <typename TF, typename TA = float, int NV = 1>
+template <typename TF, typename TA = float, int NV = 1, typename G = WinoGeom>
 __global__ void __launch_bounds__(256)
-wino2d_output_kernel(const TF* __restrict__ M, TA* __restrict__ y, WinoGeom g, long total) {
+wino2d_output_kernel(const TF* __restrict__ M, TA* __restrict__ y, G g, long total) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
-  int c, tw, th;
+  int c, h0, w0, dl;
   long tile, bd;
-  wino_decode2<NV>(i, g, c, tile, tw, th, bd);
+  wino_tile2<NV>(i, g, c, tile, h0, w0, dl, bd);
+  // (h0, w0) is inside the map for every tile; the dilated tiling's second row / column may lie beyond it
+  const long rstep = (long)dl * g.W * g.C;
+  const bool row1 = !G::kDil || h0 + dl < g.H;
   const long T = total / (g.C / NV);
   float m[NV][16];
 #pragma unroll
@@ -305,10 +343,13 @@ wino2d_output_kernel(const TF* __restrict__ M, TA* __restrict__ y, WinoGeom g, l
   if (g.acc) {                                       // y += result: old values first, then the stores
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
-      const long base = ((bd * g.H + 2 * th) * g.W + 2 * tw + f) * g.C + c;
+      if (G::kDil && w0 + f * dl >= g.W) continue;
+      const long base = ((bd * g.H + h0) * g.W + w0 + f * dl) * g.C + c;
       float t0[NV], t1[NV];
       ldv<NV>(y + base, t0);
-      ldv<NV>(y + base + (long)g.W * g.C, t1);
+#pragma unroll
+      for (int n = 0; n < NV; ++n) t1[n] = 0.0f;
+      if (row1) ldv<NV>(y + base + rstep, t1);
 #pragma unroll
       for (int n = 0; n < NV; ++n) { oldv[n][2 * f] = t0[n]; oldv[n][2 * f + 1] = t1[n]; }
     }
@@ -327,27 +368,31 @@ wino2d_output_kernel(const TF* __restrict__ M, TA* __restrict__ y, WinoGeom g, l
       y0[n] = r[0 * 2 + f] + r[1 * 2 + f] + r[2 * 2 + f] + oldv[n][2 * f];
       y1[n] = r[1 * 2 + f] - r[2 * 2 + f] - r[3 * 2 + f] + oldv[n][2 * f + 1];
     }
-    const long base = ((bd * g.H + 2 * th) * g.W + 2 * tw + f) * g.C + c;
+    if (G::kDil && w0 + f * dl >= g.W) continue;
+    const long base = ((bd * g.H + h0) * g.W + w0 + f * dl) * g.C + c;
     stv<NV>(y + base, y0);
-    stv<NV>(y + base + (long)g.W * g.C, y1);
+    if (row1) stv<NV>(y + base + rstep, y1);
   }
 }
 
-template <typename TF, typename TA = float, int NV = 1>
+template <typename TF, typename TA = float, int NV = 1, typename G = WinoGeom>
 __global__ void __launch_bounds__(256)
-wino2d_output_adjoint_kernel(const TA* __restrict__ gy, TF* __restrict__ Z, WinoGeom g, long total) {
+wino2d_output_adjoint_kernel(const TA* __restrict__ gy, TF* __restrict__ Z, G g, long total) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
-  int c, tw, th;
+  int c, h0, w0, dl;
   long tile, bd;
-  wino_decode2<NV>(i, g, c, tile, tw, th, bd);
+  wino_tile2<NV>(i, g, c, tile, h0, w0, dl, bd);
   float v[NV][16];
 #pragma unroll
   for (int e = 0; e < 2; ++e)
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
+      const int h = h0 + e * dl, w = w0 + f * dl;
       float t[NV];
-      ldv<NV>(gy + ((bd * g.H + 2 * th + e) * g.W + 2 * tw + f) * g.C + c, t);
+#pragma unroll
+      for (int n = 0; n < NV; ++n) t[n] = 0.0f;
+      if (!G::kDil || (h < g.H && w < g.W)) ldv<NV>(gy + ((bd * g.H + h) * g.W + w) * g.C + c, t);
 #pragma unroll
       for (int n = 0; n < NV; ++n) v[n][e * 4 + f] = t[n];
     }
@@ -369,7 +414,34 @@ wino2d_output_adjoint_kernel(const TA* __restrict__ gy, TF* __restrict__ Z, Wino
 }
 
 bool wino2d_ok(const ssbev_wino_dims* d) {
-  return d && d->B > 0 && d->C > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->H % 2 == 0 && d->W % 2 == 0;
+  return d && d->B > 0 && d->C > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->H % 2 == 0 && d->W % 2 == 0 && d->dil <= 1;
+}
+
+// first output coordinate of every tile along an axis of extent n, phase-major; returns the tile count (entries beyond cap are
+// counted, not written)
+int wino2d_axis_table(int n, int dil, unsigned short* first, int cap) {
+  if (n <= 0 || dil <= 0) return 0;
+  int cnt = 0;
+  for (int ph = 0; ph < dil && ph < n; ++ph) {
+    const int nt = ((n - ph + dil - 1) / dil + 1) / 2;
+    for (int t = 0; t < nt; ++t, ++cnt)
+      if (first && cnt < cap) first[cnt] = (unsigned short)(ph + 2 * t * dil);
+  }
+  return cnt;
+}
+
+// dims with dil > 1 (any H, W up to 65535, at most kWinoMaxAxisTiles tiles per axis) -> kernel geometry and thread count
+bool wino2d_dil_geom(const ssbev_wino_dims* d, WinoGeomDil& g, long& total) {
+  if (!d || d->B <= 0 || d->C <= 0 || d->D <= 0 || d->H <= 0 || d->W <= 0 || d->dil <= 1 || d->H > 65535 || d->W > 65535) return false;
+  g.B = d->B; g.D = d->D; g.H = d->H; g.W = d->W; g.C = d->C; g.acc = 0;
+  g.dil = d->dil;
+  g.TH = wino2d_axis_table(d->H, d->dil, g.h0, kWinoMaxAxisTiles);
+  g.TW = wino2d_axis_table(d->W, d->dil, g.w0, kWinoMaxAxisTiles);
+  if (g.TH > kWinoMaxAxisTiles || g.TW > kWinoMaxAxisTiles) return false;
+  for (int i = g.TH; i < kWinoMaxAxisTiles; ++i) g.h0[i] = 0;
+  for (int i = g.TW; i < kWinoMaxAxisTiles; ++i) g.w0[i] = 0;
+  total = (long)d->B * d->D * g.TH * g.TW * d->C;
+  return true;
 }
 
 // ---- weight transforms (tiny: one thread per (cin, cout) pair) ---------------------------------------------------
@@ -726,7 +798,7 @@ wino43_weight_grad_kernel(const float* __restrict__ gU, float* __restrict__ gw, 
 
 bool wino43_ok(const ssbev_wino_dims* d, int da) {
   return d && d->B > 0 && d->C > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->H % 4 == 0 && d->W % 4 == 0 &&
-         (da == 0 || d->D % da == 0);
+         (da == 0 || d->D % da == 0) && d->dil <= 1;
 }
 
 // ---- depth-fused frequency GEMM -------------------------------------------------------------------------------------
@@ -990,7 +1062,7 @@ wino_weight_packed_kernel(const float* __restrict__ w, float* __restrict__ Wp, i
 }
 
 bool wino_ok(const ssbev_wino_dims* d) {
-  return d && d->B > 0 && d->C > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->D % 2 == 0 && d->H % 2 == 0 && d->W % 2 == 0;
+  return d && d->B > 0 && d->C > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->D % 2 == 0 && d->H % 2 == 0 && d->W % 2 == 0 && d->dil <= 1;
 }
 
 }  // namespace
@@ -1014,6 +1086,31 @@ extern "C" {
     hipLaunchKernelGGL(KERNEL, dim3(cdiv((size_t)total, 256)), dim3(256), 0, as_stream(stream), src, dst, g, total); \
     return ssbev_launch_status();                                                                                  \
   }
+
+// fp32 2-D entry points: ssbev_wino_dims.dil > 1 selects the strided-tile instance of the same kernel
+#define SSBEV_WINO2D_DIL_ENTRY(NAME, KERNEL, ACC)                                                                  \
+  int NAME(const float* src, float* dst, const ssbev_wino_dims* d, ssbev_stream_t stream) {                       \
+    if (!src || !dst || !d) return SSBEV_EINVAL;                                                                   \
+    if (d->dil > 1) {                                                                                              \
+      WinoGeomDil g;                                                                                               \
+      long total;                                                                                                  \
+      if (!wino2d_dil_geom(d, g, total)) return SSBEV_EINVAL;                                                      \
+      g.acc = ACC;                                                                                                 \
+      hipLaunchKernelGGL((KERNEL<float, float, 1, WinoGeomDil>), dim3(cdiv((size_t)total, 256)), dim3(256), 0,     \
+                         as_stream(stream), src, dst, g, total);                                                   \
+      return ssbev_launch_status();                                                                                \
+    }                                                                                                              \
+    if (!wino2d_ok(d)) return SSBEV_EINVAL;                                                                        \
+    const long total = (long)d->B * d->D * (d->H / 2) * (d->W / 2) * d->C;                                         \
+    WinoGeom g{d->B, d->D, d->H, d->W, d->C};                                                                      \
+    g.acc = ACC;                                                                                                   \
+    hipLaunchKernelGGL(KERNEL<float>, dim3(cdiv((size_t)total, 256)), dim3(256), 0, as_stream(stream), src, dst, g, total); \
+    return ssbev_launch_status();                                                                                  \
+  }
+
+int ssbev_wino2d_axis_tiles(int extent, int dil, uint16_t* first, int cap) {
+  return wino2d_axis_table(extent, dil, first, first ? cap : 0);
+}
 
 int ssbev_wino_weight_transform(const float* w, float* U, int Cout, int Cin, int ndim, int mode, ssbev_stream_t stream) {
   if (!w || !U || Cout <= 0 || Cin <= 0 || (ndim != 2 && ndim != 3) || (mode != 0 && mode != 1)) return SSBEV_EINVAL;
@@ -1088,9 +1185,9 @@ int ssbev_wino_bgemm(const float* A, const float* Wp, float* Cm, int64_t T, int 
   return ssbev_launch_status();
 }
 
-SSBEV_WINO2D_ENTRY(ssbev_wino2d_input_transform, wino2d_input_kernel<float>, float, float)
-SSBEV_WINO2D_ENTRY(ssbev_wino2d_output_transform, wino2d_output_kernel<float>, float, float)
-SSBEV_WINO2D_ENTRY(ssbev_wino2d_output_adjoint, wino2d_output_adjoint_kernel<float>, float, float)
+SSBEV_WINO2D_DIL_ENTRY(ssbev_wino2d_input_transform, wino2d_input_kernel, 0)
+SSBEV_WINO2D_DIL_ENTRY(ssbev_wino2d_output_transform, wino2d_output_kernel, 0)
+SSBEV_WINO2D_DIL_ENTRY(ssbev_wino2d_output_adjoint, wino2d_output_adjoint_kernel, 0)
 
 SSBEV_WINO_ENTRY(ssbev_wino_input_transform, wino_input_kernel<float>, float, float)
 SSBEV_WINO_ENTRY(ssbev_wino_output_transform, wino_output_kernel<float>, float, float)
@@ -1133,14 +1230,7 @@ int ssbev_wino43_2d_output_transform_acc(const float* src, float* dst, const ssb
   return ssbev_launch_status();
 }
 
-int ssbev_wino2d_output_transform_acc(const float* src, float* dst, const ssbev_wino_dims* d, ssbev_stream_t stream) {
-  if (!wino2d_ok(d) || !src || !dst) return SSBEV_EINVAL;
-  const long total = (long)d->B * d->D * (d->H / 2) * (d->W / 2) * d->C;
-  WinoGeom g{d->B, d->D, d->H, d->W, d->C};
-  g.acc = 1;
-  hipLaunchKernelGGL(wino2d_output_kernel<float>, dim3(cdiv((size_t)total, 256)), dim3(256), 0, as_stream(stream), src, dst, g, total);
-  return ssbev_launch_status();
-}
+SSBEV_WINO2D_DIL_ENTRY(ssbev_wino2d_output_transform_acc, wino2d_output_kernel, 1)
 
 int ssbev_wino43_weight_transform(const float* w, float* U, int Cout, int Cin, int ndim, int mode, ssbev_stream_t stream) {
   if (!w || !U || Cout <= 0 || Cin <= 0 || (ndim != 2 && ndim != 3 && ndim != 4) || (mode != 0 && mode != 1)) return SSBEV_EINVAL;

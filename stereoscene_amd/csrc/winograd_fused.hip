@@ -518,7 +518,7 @@ wino_dfw_reduce_kernel(const float* __restrict__ gU, float* __restrict__ gw, int
 
 bool df_dims_ok(const ssbev_wino_dims* d, int N) {
   return d && d->B > 0 && d->C > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->H % 4 == 0 && d->W % 4 == 0 && d->D % 2 == 0 &&
-         d->C % DF_BK == 0 && N > 0 && N % 4 == 0;       // (N % 4: 16-byte stores of the output rows)
+         d->C % DF_BK == 0 && N > 0 && N % 4 == 0 && d->dil <= 1;       // (N % 4: 16-byte stores of the output rows)
 }
 
 int env_int(const char* name, int dflt) {

@@ -1171,8 +1171,33 @@ def conv_transpose3d(x, weight, bias=None, stride=1, padding=0, output_padding=0
 # dilation 6 / 12 / 18 on the 48 x 160 map) are therefore sent through the Winograd path as a batch of d*d small images
 # (space-to-batch / batch-to-space are two tensor copies of 20 MB): 2.25x fewer multiply-adds than the direct dilated
 # kernel.  Only when zero-padding the map to multiples of 2d costs < 35 % extra pixels (not for d = 18 at 48 x 160).
+# (The route of the bf16 modes, and of fp32 with SSBEV_WINO_DILATED=0; fp32 otherwise takes the strided-tile transforms below.)
 DILATED_POLYPHASE = os.environ.get("SSBEV_DILATED_POLYPHASE", "1") != "0"
 POLYPHASE_MAX_PAD = float(os.environ.get("SSBEV_POLYPHASE_MAX_PAD", "1.35"))
+
+
+# fp32: the residue classes are an addressing pattern of the F(2x2, 3x3) transform kernels (csrc/winograd.hip, ssbev_wino_dims.dil),
+# not a data layout: every class is tiled on its own, so nothing is padded to multiples of 2d and no sub-image batch is built
+# (no pad / permute clone / to_cl clone / slice, forward or backward).  Tiles per axis = sum over the classes ph < min(d, n) of
+# ceil(ceil((n - ph) / d) / 2) (ssbev_wino2d_axis_tiles).  The route is taken while that costs at most WINO_DILATED_MAX_TILES
+# times the tiles of the undilated layer: POLYPHASE_MAX_PAD + 0.05 = 1.40 admits the ASPP d = 18 branch (30 x 88 tiles against
+# 24 x 80 = 1.375x), which at 2.25 / 1.375 is still 1.64x fewer multiply-adds than the direct dilated kernels.
+# SSBEV_WINO_DILATED=0: the polyphase batch / direct kernels as before (A/B runs).
+WINO_DILATED = os.environ.get("SSBEV_WINO_DILATED", "1") != "0"
+WINO_DILATED_MAX_TILES = float(os.environ.get("SSBEV_WINO_DILATED_MAX_TILES", str(POLYPHASE_MAX_PAD + 0.05)))
+WINO_DILATED_AXIS_CAP = 128          # tile-table entries per axis the transform kernels take (SSBEV_WINO2D_MAX_AXIS_TILES)
+
+
+def wino2d_axis_tiles(n, d):
+    """F(2,3) tiles along an axis of extent ``n`` when each residue class modulo ``d`` is tiled on its own."""
+    return sum(-(-(-(-(n - ph) // d)) // 2) for ph in range(min(d, n)))
+
+
+def _wino_dilated_applicable(x, weight, d):
+    H, W = int(x.shape[-2]), int(x.shape[-1])
+    th, tw = wino2d_axis_tiles(H, d), wino2d_axis_tiles(W, d)
+    return (max(th, tw) <= WINO_DILATED_AXIS_CAP and weight.shape[1] % 4 == 0
+            and th * tw <= WINO_DILATED_MAX_TILES * (-(-H // 2)) * (-(-W // 2)))
 
 
 def _dilated_polyphase(x, weight, d):
@@ -1209,6 +1234,11 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1):
     if (GEMM_LAYERS and TILE_HINT == 0 and PRECISION == "fp32" and x.is_cuda and tuple(weight.shape[2:]) == (1, 1)
             and s == (1, 1) and p == (0, 0) and weight.shape[1] >= GEMM_MIN_CIN):
         return linear_cl(x, weight, bias)           # wide pointwise conv = plain GEMM on the channels-last buffer
+    if (WINO_DILATED and WINOGRAD and TILE_HINT == 0 and PRECISION == "fp32" and x.is_cuda and tuple(weight.shape[2:]) == (3, 3)
+            and s == (1, 1) and dl[0] == dl[1] and dl[0] > 1 and p == dl and min(weight.shape[0], weight.shape[1]) >= 64
+            and _wino_dilated_applicable(x, weight, dl[0])):
+        y = _WinoConv.apply(x.unsqueeze(2), weight.unsqueeze(2), _slot_of(x), dl[0]).squeeze(2)
+        return y if bias is None else y + bias.view(1, -1, 1, 1)
     if (DILATED_POLYPHASE and WINOGRAD and TILE_HINT == 0 and x.is_cuda and tuple(weight.shape[2:]) == (3, 3) and s == (1, 1)
             and dl[0] == dl[1] and dl[0] > 1 and p == dl and min(weight.shape[0], weight.shape[1]) >= 64):
         y = _dilated_polyphase(x, weight, dl[0])
@@ -1525,13 +1555,14 @@ class _WinoConvDF(torch.autograd.Function):
 class _WinoConv(torch.autograd.Function):
     """3x3(x3) / stride 1 / pad 1 convolution in the Winograd domain: HIP transforms + NF plain GEMMs.  x logical
     [B,Cin,D,H,W] channels-last, weight [Cout,Cin,kd,3,3] with kd = 3 (3-D, even D) or kd = 1 (2-D over (H,W); D is a
-    batch axis).  Tiles: F(4,3) along h and w when both are multiples of 4 (NF = 144 / 36), else F(2,3) (NF = 64 / 16)."""
+    batch axis).  Tiles: F(4,3) along h and w when both are multiples of 4 (NF = 144 / 36), else F(2,3) (NF = 64 / 16).
+    ``dil`` > 1 (2-D fp32 only): dilation = padding = dil on the strided-tile F(2,3) transforms (see WINO_DILATED); any H, W."""
 
     @staticmethod
-    def _plan(three_d, D, H, W, bf, cin=1 << 30):
+    def _plan(three_d, D, H, W, bf, cin=1 << 30, dil=1):
         # bf16 mode stays on F(2,3): its +-1 transforms add no error of their own, while the F(4,3) matrices amplify the
         # bf16 rounding of V / M by their 4 / 5 / 8 entries (measured: 11 % max error against 1 % for F(2,3))
-        f43 = WINO_F43 and (three_d or WINO_F43_2D or _F43_2D_SCOPE > 0) and not bf and H % 4 == 0 and W % 4 == 0 and \
+        f43 = WINO_F43 and (three_d or WINO_F43_2D or _F43_2D_SCOPE > 0) and not bf and H % 4 == 0 and W % 4 == 0 and dil == 1 and \
             not (three_d and (WINO_DEPTH_FUSED or WINO_OWN_GEMM))
         if f43 and three_d and WINO_F444 and D % 4 == 0 and cin >= WINO_F444_MIN_CIN:
             return 4, "ssbev_wino444_", 216, 4, 8.0
@@ -1544,17 +1575,24 @@ class _WinoConv(torch.autograd.Function):
         return (1 if f43 else 0), pre, nf, th, reduction
 
     @staticmethod
-    def forward(ctx, x, weight, slot=None):
+    def forward(ctx, x, weight, slot=None, dil=1):
         ctx.slot = slot
         if ctx.needs_input_grad[1]:
             streams.note_use(weight)
         bf = PRECISION != "fp32"
+        if dil > 1 and (bf or weight.shape[2] != 1):
+            raise capi.SsbevError("dilated Winograd: 2-D fp32 layers only")
         a16 = storage_bf16()              # bf16 tensors on the activation side too (`_bf16a` transforms)
         xcl = to_cl(x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)) if a16 else to_cl(_f32(x, "wino_conv"))
         B, D, H, W, Cin = xcl.shape
         Cout, three_d = weight.shape[0], weight.shape[2] == 3
-        f43, pre, nf, th, red = _WinoConv._plan(three_d, D, H, W, bf, Cin)
+        f43, pre, nf, th, red = _WinoConv._plan(three_d, D, H, W, bf, Cin, dil)
         T = B * (D // (4 if f43 == 4 else 2) if three_d else D) * (H // th) * (W // th)
+        dtag = ""
+        if dil > 1:                       # every residue class tiled on its own: more tiles than (H / 2) (W / 2)
+            T = B * D * wino2d_axis_tiles(H, dil) * wino2d_axis_tiles(W, dil)
+            red *= B * D * H * W / (4.0 * T)
+            dtag = f" d{dil}"
         lib = capi.load()
         w = weight.detach().contiguous()
         fl = 2.0 * B * D * H * W * Cin * Cout * (27 if three_d else 9)
@@ -1564,7 +1602,7 @@ class _WinoConv(torch.autograd.Function):
         if not fused:
             U = torch.empty(nf, Cin, Cout, dtype=torch.float32, device=x.device)
             capi.check(wt(capi.ptr(w), capi.ptr(U), Cout, Cin, wdim, 0, capi.stream()), "ssbev_wino_weight_transform")
-        tag = f"wino{ {0: '', 1: '43', 4: '444'}[f43]} fwd {Cin}->{Cout} {D}x{H}x{W}"
+        tag = f"wino{ {0: '', 1: '43', 4: '444'}[f43]} fwd {Cin}->{Cout} {D}x{H}x{W}{dtag}"
         nby = 4.0 * (B * D * H * W * (Cin + Cout) + (27 if three_d else 9) * Cin * Cout)
         with _span("conv_winograd", fl, nby, tag, fl / red):
             if fused:      # (h,w)-transformed tensors only (4x), the depth axis of F(2,3) inside the GEMM kernel
@@ -1572,22 +1610,23 @@ class _WinoConv(torch.autograd.Function):
                 V = None
             elif bf:
                 sfx = "_bf16a" if a16 else "_bf16"
-                V = _wino_call(pre + "input_transform" + sfx, xcl, capi.WinoDims(B, D, H, W, Cin), (nf, T, Cin), torch.bfloat16)
+                V = _wino_call(pre + "input_transform" + sfx, xcl, capi.WinoDims(B, D, H, W, Cin, dil), (nf, T, Cin), torch.bfloat16)
                 M = _bmm16(V, U)
-                y = _wino_call(pre + "output_transform" + sfx, M, capi.WinoDims(B, D, H, W, Cout), (B, D, H, W, Cout),
+                y = _wino_call(pre + "output_transform" + sfx, M, capi.WinoDims(B, D, H, W, Cout, dil), (B, D, H, W, Cout),
                                torch.bfloat16 if a16 else torch.float32)
             else:
-                V = _wino_call(pre + "input_transform", xcl, capi.WinoDims(B, D, H, W, Cin), (nf, T, Cin))
+                V = _wino_call(pre + "input_transform", xcl, capi.WinoDims(B, D, H, W, Cin, dil), (nf, T, Cin))
                 M = _wino_bgemm(V, w, Cout, Cin, 0) if (three_d and WINO_OWN_GEMM and not f43) else (gemm_nn(V, U, tag=tag + " gemm") if own_gemm_site("wino") else torch.bmm(V, U))
-                y = _wino_call(pre + "output_transform", M, capi.WinoDims(B, D, H, W, Cout), (B, D, H, W, Cout))
+                y = _wino_call(pre + "output_transform", M, capi.WinoDims(B, D, H, W, Cout, dil), (B, D, H, W, Cout))
         ctx.save_for_backward(xcl if fused else V, weight)
-        ctx.geom = (B, D, H, W, Cin, Cout, T, three_d, fl, fused, bf, f43, pre, nf, red, a16)
+        ctx.geom = (B, D, H, W, Cin, Cout, T, three_d, fl, fused, bf, f43, pre, nf, red, a16, dil)
         return from_cl(y)
 
     @staticmethod
     def backward(ctx, gy):
         V, weight = ctx.saved_tensors            # (depth-fused path: V is the channels-last input, transformed below)
-        B, D, H, W, Cin, Cout, T, three_d, fl, fused, bf, f43, pre, nf, red, a16 = ctx.geom
+        B, D, H, W, Cin, Cout, T, three_d, fl, fused, bf, f43, pre, nf, red, a16, dil = ctx.geom
+        dtag = f" d{dil}" if dil > 1 else ""
         sfx, fdt = (("_bf16a" if a16 else "_bf16"), torch.bfloat16) if bf else ("", torch.float32)
         gcl = to_cl(gy)
         if a16 and gcl.dtype != torch.bfloat16:
@@ -1606,8 +1645,8 @@ class _WinoConv(torch.autograd.Function):
             Ut = torch.empty(nf, Cout, Cin, dtype=torch.float32, device=gy.device)
             wt = lib.ssbev_wino43_weight_transform if f43 else lib.ssbev_wino_weight_transform
             capi.check(wt(capi.ptr(w), capi.ptr(Ut), Cout, Cin, nd, 1, capi.stream()), "ssbev_wino_weight_transform")
-            with _span("conv_winograd", fl, nby, f"wino{vtag} dgrad {Cin}->{Cout} {D}x{H}x{W}", fl / red):
-                Vg = _wino_call(pre + "input_transform" + sfx, gcl, capi.WinoDims(B, D, H, W, Cout), (nf, T, Cout), fdt)
+            with _span("conv_winograd", fl, nby, f"wino{vtag} dgrad {Cin}->{Cout} {D}x{H}x{W}{dtag}", fl / red):
+                Vg = _wino_call(pre + "input_transform" + sfx, gcl, capi.WinoDims(B, D, H, W, Cout, dil), (nf, T, Cout), fdt)
                 Mx = _wino_bgemm(Vg, w, Cout, Cin, 1) if (three_d and WINO_OWN_GEMM and not bf and not f43) \
                     else ((_bmm16(Vg, Ut) if fdt == torch.bfloat16 else torch.bmm(Vg, Ut.to(fdt))) if (bf or not own_gemm_site("wino")) else gemm_nn(Vg, Ut, tag="wino dgrad gemm"))
                 del Vg
@@ -1615,20 +1654,20 @@ class _WinoConv(torch.autograd.Function):
                           "ssbev_wino43_2d_": "ssbev_wino43_2d_output_transform_acc"}.get(pre) if not bf else None
                 into = _slot_target(ctx.slot, torch.empty((B, D, H, W, Cin), device="meta")) if acc_fn else None
                 if into is not None:
-                    odims = capi.WinoDims(B, D, H, W, Cin)
+                    odims = capi.WinoDims(B, D, H, W, Cin, dil)
                     capi.check(getattr(lib, acc_fn)(capi.ptr(Mx), capi.ptr(into), C.byref(odims), capi.stream()), acc_fn)
                     gxcl = into
                 else:
-                    gxcl = _wino_call(pre + "output_transform" + sfx, Mx, capi.WinoDims(B, D, H, W, Cin), (B, D, H, W, Cin), adt)
+                    gxcl = _wino_call(pre + "output_transform" + sfx, Mx, capi.WinoDims(B, D, H, W, Cin, dil), (B, D, H, W, Cin), adt)
                 if ctx.slot is not None:
                     ctx.slot.buf = gxcl
             gx = from_cl(gxcl)
         if ctx.needs_input_grad[1]:
             def weight_gradient(V=V):
-                with _span("conv_winograd_wgrad", fl, nby, f"wino{vtag} wgrad {Cin}->{Cout} {D}x{H}x{W}", fl / red):
+                with _span("conv_winograd_wgrad", fl, nby, f"wino{vtag} wgrad {Cin}->{Cout} {D}x{H}x{W}{dtag}", fl / red):
                     if fused:
-                        V = _wino_call(pre + "input_transform", V, capi.WinoDims(B, D, H, W, Cin), (nf, T, Cin))
-                    Z = _wino_call(pre + "output_adjoint" + sfx, gcl, capi.WinoDims(B, D, H, W, Cout), (nf, T, Cout), fdt)
+                        V = _wino_call(pre + "input_transform", V, capi.WinoDims(B, D, H, W, Cin, dil), (nf, T, Cin))
+                    Z = _wino_call(pre + "output_adjoint" + sfx, gcl, capi.WinoDims(B, D, H, W, Cout, dil), (nf, T, Cout), fdt)
                     gU = _bmm16_tn(V, Z) if bf else (gemm_tn(V, Z, tag="wino wgrad gemm") if own_gemm_site("wino") else torch.bmm(V.transpose(1, 2), Z))
                 gwt = torch.empty_like(w)
                 wg = lib.ssbev_wino43_weight_grad if f43 else lib.ssbev_wino_weight_grad
@@ -1641,7 +1680,7 @@ class _WinoConv(torch.autograd.Function):
                     side.publish(gw)
             else:
                 gw = weight_gradient()
-        return gx, gw, None
+        return gx, gw, None, None
 
 
 def conv_flops_3x3(B, D, H, W, Cin, Cout):
