@@ -509,6 +509,42 @@ int ssbev_ohem_ce_bwd(const float* logits, const uint8_t* label, const float* cl
                       const float* inv_wsum, const float* grad_out, float* grad_logits, const ssbev_ohem_dims* d, void* ws,
                       size_t ws_bytes, ssbev_stream_t stream);
 
+/* Frustum-proportion voxel loss (since version 112): compute_frustum_dist_loss(up(logits), masks, dists) of the reference
+ * (utils/semkitti.py:218-244) with the 64 disjoint bool masks of a sample held as ONE byte per voxel (the frustum id, 255 = none).
+ * p = softmax over the classes; cum[f][c] = sum over the batch and the voxels with id f of p[c]; cnt[f][c] = sum over the batch of
+ * dists[b][f][c]; a frustum counts if sum_c cum > 0 and sum_c cnt > 0; its term is sum over the classes with t_c != 0 of
+ * t_c (log t_c - log q_c), t = cnt[f] / sum, q = cum[f] / sum; loss = sum of the terms / number of counted frusta, and 0 (the
+ * reference divides 0 / 0) when no frustum counts.  The up-sampled logits are never written.
+ *   dims      B, D, H, W: the LOGITS' grid; C == 20; F in 1..64 frusta; upsample 0 / 1 as in ssbev_ohem_dims
+ *   logits    [B, D, H, W, 20] channels-last fp32;  ids [B, D', H', W'] uint8 (a value >= F names no frustum)
+ *   dists     [B, F, 20] float (device)
+ *   loss      one float (device)
+ *   g         [F, 20] float (device), kept by the caller for backward: d loss / d cum
+ *   backward  grad_logits [B, D, H, W, 20] = grad_out[0] * d loss / d logits (grad_out: one float on the device); dists carry no
+ *             gradient
+ * One pass over the fine voxels with per-wave row tables in LDS (a cross-lane sum per distinct id of the wave), per-workgroup
+ * partial tables in double, fixed-order sums: no float atomics, nothing read back, every run gives the same bits.
+ * SSBEV_EINVAL before any device work: NULL pointers, non-positive dims, C != 20, F outside 1..64, upsample not 0 / 1,
+ * 20 x voxels >= 2^31;  SSBEV_EWORKSPACE: ws_bytes below the query.  The queries answer 0 for refused dims. */
+typedef struct { int B, D, H, W, C, F, upsample; } ssbev_frustum_dims;
+size_t ssbev_frustum_dist_workspace(const ssbev_frustum_dims* d);
+int ssbev_frustum_dist_fwd(const float* logits, const uint8_t* ids, const float* dists, float* loss, float* g,
+                           const ssbev_frustum_dims* d, void* ws, size_t ws_bytes, ssbev_stream_t stream);
+size_t ssbev_frustum_dist_bwd_workspace(const ssbev_frustum_dims* d);
+int ssbev_frustum_dist_bwd(const float* logits, const uint8_t* ids, const float* g, const float* grad_out, float* grad_logits,
+                           const ssbev_frustum_dims* d, void* ws, size_t ws_bytes, ssbev_stream_t stream);
+/* The loader step CreateRelationLabels (datasets/pipelines/voxel_labels.py:201-265 of the reference) on the device: the frustum id
+ * of every voxel of a label grid and the class counts of every frustum.
+ *   labels   [X, Y, Z] uint8 (device; a value >= 20 counts as unlabelled);  ids [X, Y, Z] uint8 (device): py * frustum_size + px,
+ *            255 when the centre lies in no patch, at depth <= 0 or the voxel is unlabelled;  counts [frustum_size^2][20] int32
+ *            (device; zeroed here, integer atomics: exact)
+ *   params   24 floats on the HOST: centre of voxel (0, 0, 0) [3], voxel size [3], the row-major 3x4 matrix that takes a centre to
+ *            (x d, y d, d) [12], the 2x2 post-rotation [4], the post-translation [2]
+ *   patch i along an axis is [i / frustum_size * size, (i + 1) / frustum_size * size), the products in double rounded to fp32
+ * SSBEV_EINVAL: NULL pointers, non-positive dims or image size, frustum_size outside 1..8, X Y Z >= 2^31. */
+int ssbev_frustum_labels(const uint8_t* labels, uint8_t* ids, int32_t* counts, int X, int Y, int Z, const float* params,
+                         int img_h, int img_w, int frustum_size, ssbev_stream_t stream);
+
 /* Running statistics of a training-mode BatchNorm from the (mean, rstd) ssbev_groupnorm_fwd returned with G == C over the
  * batch: running_mean <- (1-m) running_mean + m mean; running_var <- (1-m) running_var + m var n/(n-1)
  * (torch.nn.BatchNorm3d as built at ViewTransformerLSSVoxel.py:83-88; n = elements per channel). */

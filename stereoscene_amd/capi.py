@@ -94,6 +94,10 @@ class OhemDims(C.Structure):
     _fields_ = LovaszDims._fields_ + [("top_k", C.c_double)]
 
 
+class FrustumDims(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("B", "D", "H", "W", "C", "F", "upsample")]
+
+
 class GemmDims(C.Structure):
     _fields_ = [("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("batch", C.c_int),
                 ("lda", C.c_int64), ("ldb", C.c_int64), ("ldc", C.c_int64), ("sa", C.c_int64), ("sb", C.c_int64), ("sc", C.c_int64),
@@ -305,6 +309,11 @@ SIGNATURES = {
     "ssbev_ohem_ce_fwd": (C.c_int, [_P] * 6 + [C.POINTER(OhemDims), _P, C.c_size_t, _P]),
     "ssbev_ohem_ce_bwd_workspace": (C.c_size_t, [C.POINTER(OhemDims)]),
     "ssbev_ohem_ce_bwd": (C.c_int, [_P] * 7 + [C.POINTER(OhemDims), _P, C.c_size_t, _P]),
+    "ssbev_frustum_dist_workspace": (C.c_size_t, [C.POINTER(FrustumDims)]),
+    "ssbev_frustum_dist_fwd": (C.c_int, [_P] * 5 + [C.POINTER(FrustumDims), _P, C.c_size_t, _P]),
+    "ssbev_frustum_dist_bwd_workspace": (C.c_size_t, [C.POINTER(FrustumDims)]),
+    "ssbev_frustum_dist_bwd": (C.c_int, [_P] * 5 + [C.POINTER(FrustumDims), _P, C.c_size_t, _P]),
+    "ssbev_frustum_labels": (C.c_int, [_P] * 3 + [C.c_int] * 3 + [_P] + [C.c_int] * 3 + [_P]),
     "ssbev_grad_norm_workspace": (C.c_size_t, []),
     "ssbev_grad_norm": (C.c_int, [_P, C.c_int64, _P, _P, C.c_size_t, _P]),
     "ssbev_adamw_step": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.POINTER(AdamWCfg), _P, _P]),

@@ -2463,6 +2463,158 @@ def ohem_ce_loss(logits, label_u8, class_weight, top_k=0.25):
     return losses.ohem_ce_loss(logits, label_u8, class_weight, top_k).float()
 
 
+FRUSTUM_DIST = os.environ.get("SSBEV_FRUSTUM_DIST", "1") != "0"    # fused frustum-proportion loss (0 = the tensor form: one scatter-add over the up-sampled softmax)
+FRUSTUM_NONE = 255                                                 # id of a voxel that lies in no frustum
+
+
+def frustum_dist_supported(logits, ids, dists):
+    """The fused frustum-proportion loss serves what the fused Lovasz-softmax serves (fp32 20-class logits on the GPU that sit on
+    the id grid or at exactly half of it) with uint8 ids and counts [B, F, 20] of at most 64 frusta."""
+    return (lovasz_supported(logits, ids) and ids.dtype == torch.uint8 and ids.device == logits.device
+            and torch.is_tensor(dists) and dists.dim() == 3
+            and dists.shape[0] == logits.shape[0] and 1 <= dists.shape[1] <= 64 and dists.shape[2] == 20)
+
+
+def frustum_ids_from_masks(masks):
+    """The reference's dense bool ``frustums_masks`` [B, F, X, Y, Z] (or [F, X, Y, Z]) -> the id volume uint8 [B, X, Y, Z]
+    ([X, Y, Z]): the index of the mask that holds the voxel, 255 for none.  ``None`` when two masks overlap somewhere (the masks of
+    ``CreateRelationLabels`` never do: a centre projects into one half-open patch) or with more than 255 masks; the caller then
+    uses the dense tensor form.  The overlap test reads one scalar back: pass ``frustums_ids`` to avoid it."""
+    m = masks.bool()
+    dim = m.dim() - 4
+    if m.shape[dim] > 255:
+        return None
+    if bool((m.sum(dim, dtype=torch.int32) > 1).any()):
+        return None
+    first = m.to(torch.uint8).argmax(dim).to(torch.uint8)
+    return torch.where(m.any(dim), first, torch.full_like(first, FRUSTUM_NONE))
+
+
+class _FrustumDist(torch.autograd.Function):
+    """logits [B,20,D,H,W], ids uint8 [B,D',H',W'] (the same grid or exactly twice it), counts [B,F,20] -> the frustum-proportion
+    loss (0-dim fp32), ``ssbev_frustum_dist_fwd / _bwd``.  Forward keeps the F x 20 coefficient table d loss / d cum on the device;
+    nothing is read back.  No gradient for the counts."""
+
+    @staticmethod
+    def forward(ctx, logits, ids_u8, dists):
+        lib = capi.load()
+        xcl = to_cl(_f32(logits, "frustum_dist_loss"))
+        B, D, H, W, Cch = xcl.shape
+        ids = ids_u8.contiguous()
+        up = int(tuple(ids.shape[1:]) != (D, H, W))
+        dev = logits.device
+        cnt = dists.detach().to(device=dev, dtype=torch.float32).contiguous()
+        d = capi.FrustumDims(B, D, H, W, Cch, cnt.shape[1], up)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        g = torch.empty(cnt.shape[1], Cch, dtype=torch.float32, device=dev)
+        ws = _ws(lib.ssbev_frustum_dist_workspace(C.byref(d)), dev)
+        # one pass reads the logits' taps and one byte per voxel; the partial tables are small
+        with _span("frustum", 0.0, 4.0 * xcl.numel() + ids.numel() + 2.0 * ws.numel(), "fwd   frustum"):
+            capi.check(lib.ssbev_frustum_dist_fwd(capi.ptr(xcl), capi.ptr(ids), capi.ptr(cnt), capi.ptr(loss), capi.ptr(g),
+                                                  C.byref(d), capi.ptr(ws), ws.numel(), capi.stream()), "ssbev_frustum_dist_fwd")
+        ctx.save_for_backward(xcl, ids, g)
+        ctx.dims = d
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = capi.load()
+        xcl, ids, g = ctx.saved_tensors
+        d = ctx.dims
+        gl = gout.to(torch.float32).reshape(1).contiguous()
+        gx = torch.empty_like(xcl)
+        ws = _ws(lib.ssbev_frustum_dist_bwd_workspace(C.byref(d)), xcl.device)
+        with _span("frustum", 0.0, 8.0 * xcl.numel() + ids.numel() + 8.0 * 20 * ids.numel() * d.upsample, "bwd   frustum"):
+            capi.check(lib.ssbev_frustum_dist_bwd(capi.ptr(xcl), capi.ptr(ids), capi.ptr(g), capi.ptr(gl), capi.ptr(gx), C.byref(d),
+                                                  capi.ptr(ws), ws.numel(), capi.stream()), "ssbev_frustum_dist_bwd")
+        return from_cl(gx), None, None
+
+
+def frustum_dist_loss(logits, ids_u8, dists):
+    """Frustum-proportion loss of ``up(logits)`` against the frustum ids ``ids_u8`` (255 = in no frustum) and the class counts
+    ``dists`` [B,F,20]: per frustum, pooled over the batch, the KL divergence (over the classes with a non-zero count) between the
+    labelled class mix and the predicted one, averaged over the frusta that hold both voxels and counts; 0 with a zero gradient
+    when there is none; fp32, 0-dim; no gradient for ``dists``.  Supported inputs (``frustum_dist_supported``) with
+    ``FRUSTUM_DIST`` on run on the fused HIP path; anything else on the tensor form of plugin/losses.py after
+    ``upsample_trilinear``."""
+    ids_u8 = ids_u8.to(device=logits.device, dtype=torch.uint8)       # (the loader step's output may still live on the host)
+    if FRUSTUM_DIST and frustum_dist_supported(logits, ids_u8, dists):
+        return _FrustumDist.apply(logits, ids_u8, dists)
+    from .plugin import losses
+    if not FRUSTUM_DIST and logits.is_cuda:
+        up = upsample_trilinear(logits, ids_u8.shape[-3:])
+        return losses.frustum_dist_tensor(up, ids_u8, dists.detach().to(up)).float()
+    return losses.frustum_dist_loss(logits, ids_u8, dists).float()
+
+
+def frustum_view_matrix(view):
+    """The loader step's camera of one sample of a view (``img_inputs[k]``: imgs, rots, trans, intrins, post_rots, post_trans,
+    bda, ...; of one sample, or the first sample of a batch) -> (M float64 [3,4] that takes a point of the (BEV-augmented) label grid to
+    (x d, y d, d): inverse BEV matrix (3x3, or 4x4 applied to the homogeneous point), minus ``trans``, inverse ``rots``, the 4x4
+    ``intrins``; post-rotation float64 [2,2]; post-translation float64 [2]; (img_h, img_w)), composed on the host in float64."""
+    imgs, rots, trans, intrins, post_rots, post_trans, bda = view[:7]
+
+    def mat(t, r, c):
+        t = torch.as_tensor(t).detach().double().cpu()
+        t = t.reshape(-1, r, c) if t.numel() > r * c else t.reshape(1, r, c)
+        return t[0]
+    bda = torch.as_tensor(bda)
+    n = int(bda.shape[-1])
+    inv_bda = torch.eye(4, dtype=torch.float64)
+    inv_bda[:n, :n] = torch.inverse(mat(bda, n, n))
+    A, a = inv_bda[:3, :3], inv_bda[:3, 3]
+    Rinv = torch.inverse(mat(rots, 3, 3))
+    K = mat(intrins, 4, 4)
+    t = mat(trans, 1, 3).reshape(3)
+    KR = K[:3, :3] @ Rinv
+    M = torch.cat([KR @ A, (KR @ (a - t) + K[:3, 3]).reshape(3, 1)], dim=1)
+    pr = mat(post_rots, 3, 3)[:2, :2].clone()
+    pt = mat(post_trans, 1, 3).reshape(3)[:2].clone()
+    return M, pr, pt, tuple(int(v) for v in imgs.shape[-2:])
+
+
+def frustum_labels(labels, view, point_cloud_range, frustum_size=8):
+    """The loader step ``CreateRelationLabels`` of one sample: voxel labels [X,Y,Z] (255 = unlabelled) and one view of
+    ``img_inputs`` -> (ids uint8 [X,Y,Z]: ``py * frustum_size + px`` of the image patch the voxel centre projects into, 255 for no
+    patch, a depth <= 0 or an unlabelled voxel; counts float32 [frustum_size^2, 20]: labelled voxels per frustum and class).  CUDA
+    labels run ``ssbev_frustum_labels``; CPU labels the same fp32 arithmetic in tensor ops.  The camera is composed on the host
+    in float64 (``frustum_view_matrix``) and rounded to fp32 once.  The image size is that of ``view[0]``."""
+    fs = int(frustum_size)
+    if not 1 <= fs <= 8:
+        raise ValueError(f"frustum_labels: frustum_size must be in 1..8, got {frustum_size}")
+    M, pr, pt, (img_h, img_w) = frustum_view_matrix(view)
+    X, Y, Z = (int(v) for v in labels.shape)
+    r = torch.as_tensor(point_cloud_range, dtype=torch.float64).reshape(6)
+    size = (r[3:] - r[:3]) / torch.tensor([X, Y, Z], dtype=torch.float64)
+    params = torch.cat([r[:3] + size / 2, size, M.reshape(-1), pr.reshape(-1), pt.reshape(-1)]).float().contiguous()
+    if labels.is_cuda:
+        lib = capi.load()
+        lab = labels.to(torch.uint8).contiguous()
+        ids = torch.empty_like(lab)
+        counts = torch.empty(fs * fs, 20, dtype=torch.int32, device=lab.device)
+        capi.check(lib.ssbev_frustum_labels(capi.ptr(lab), capi.ptr(ids), capi.ptr(counts), X, Y, Z, C.c_void_p(params.data_ptr()),
+                                            img_h, img_w, fs, capi.stream()), "ssbev_frustum_labels")
+        return ids, counts.float()
+    o, s, m = params[0:3], params[3:6], params[6:18].reshape(3, 4)
+    cx = (o[0] + torch.arange(X, dtype=torch.float32) * s[0]).view(X, 1, 1)
+    cy = (o[1] + torch.arange(Y, dtype=torch.float32) * s[1]).view(1, Y, 1)
+    cz = (o[2] + torch.arange(Z, dtype=torch.float32) * s[2]).view(1, 1, Z)
+    xd, yd, d = (m[i, 0] * cx + m[i, 1] * cy + m[i, 2] * cz + m[i, 3] for i in range(3))
+    u0, v0 = xd / d, yd / d
+    pu = params[18] * u0 + params[19] * v0 + params[22]
+    pv = params[20] * u0 + params[21] * v0 + params[23]
+    ex = torch.tensor([i / fs * img_w for i in range(fs + 1)], dtype=torch.float64).float()
+    ey = torch.tensor([i / fs * img_h for i in range(fs + 1)], dtype=torch.float64).float()
+    px = torch.bucketize(pu.contiguous(), ex, right=True) - 1                    # ex[px] <= pu < ex[px + 1]
+    py = torch.bucketize(pv.contiguous(), ey, right=True) - 1
+    lab = labels.long()
+    ok = (px >= 0) & (px < fs) & (py >= 0) & (py < fs) & (d > 0) & (lab < 20) & ~torch.isnan(pu) & ~torch.isnan(pv)
+    ids = torch.where(ok, py * fs + px, torch.full_like(px, FRUSTUM_NONE)).to(torch.uint8)
+    counts = torch.zeros(fs * fs * 20, dtype=torch.float32)
+    counts.index_add_(0, (ids.long() * 20 + lab)[ok], torch.ones(int(ok.sum()), dtype=torch.float32))
+    return ids, counts.view(fs * fs, 20)
+
+
 DEPTH_BCE = os.environ.get("SSBEV_DEPTH_BCE", "1") != "0"    # fused depth loss (0 = the ~35 ATen ops of the tensor expression)
 
 

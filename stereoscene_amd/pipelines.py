@@ -153,6 +153,45 @@ class CreateDepthFromLiDAR:
         return results
 
 
+@PIPELINES.register_module()
+class CreateRelationLabels:
+    """Pipeline step ``CreateRelationLabels`` (datasets/pipelines/voxel_labels.py:65-265), the part the upstream runs: the
+    frustum of every voxel of ``results['gt_occ']`` and the class counts per frustum, the inputs of the head's frustum-proportion
+    loss (``frustum_dist``).  Adds ``frustums_ids`` (uint8 [X,Y,Z]: ``py * 8 + px`` of the image patch the voxel centre projects
+    into, 255 for none) and ``frustums_class_dists`` (float [64,20]); with ``dense_masks=True`` also the upstream's
+    ``frustums_masks`` (bool [64,X,Y,Z], 64 bytes per voxel).  ``device``: where the step runs (``None``: where ``gt_occ`` lives;
+    on the GPU it is one kernel, ``functional.frustum_labels``).
+    The upstream step unpacks ``results['img_inputs'][:7]`` as ONE view and fails on this model's stereo input, where
+    ``img_inputs`` is the tuple (left view, right view) (voxel_labels.py:252).  Here the LEFT view (``img_inputs[0]``) is used when
+    ``img_inputs`` holds views, and ``img_inputs`` itself when its first entry is a tensor (the single-view layout the step was
+    written for).  The relation matrix of the same class (``compute_CP_mega_matrix``) is commented out upstream and not built;
+    ``output_scale`` is accepted and, as upstream, unused."""
+
+    def __init__(self, point_cloud_range, grid_size, class_names, output_scale=2.0, dense_masks=False, device=None):
+        self.grid_size = np.array(grid_size)
+        self.point_cloud_range = np.array(point_cloud_range, dtype=np.float64)
+        self.class_names, self.n_classes, self.output_scale = class_names, len(class_names), output_scale
+        if self.n_classes != 20:
+            raise NotImplementedError("CreateRelationLabels is built for the 20 SemanticKITTI classes")
+        self.dense_masks, self.device = bool(dense_masks), device
+        self.frustum_size = 8
+
+    def __call__(self, results):
+        from . import functional as F
+        labels = torch.as_tensor(results["gt_occ"])
+        if tuple(labels.shape) != tuple(int(v) for v in self.grid_size):
+            raise ValueError(f"CreateRelationLabels: gt_occ {tuple(labels.shape)} is not the grid {tuple(self.grid_size)}")
+        inputs = results["img_inputs"]
+        view = inputs if torch.is_tensor(inputs[0]) else inputs[0]
+        lab = labels if self.device is None else labels.to(self.device)
+        ids, counts = F.frustum_labels(lab, view, self.point_cloud_range, self.frustum_size)
+        results["frustums_ids"], results["frustums_class_dists"] = ids, counts
+        if self.dense_masks:
+            f = torch.arange(self.frustum_size ** 2, device=ids.device, dtype=torch.uint8).view(-1, 1, 1, 1)
+            results["frustums_masks"] = ids.unsqueeze(0) == f
+        return results
+
+
 # -------------------------------------------------------------------------------------------------
 # Image loading: Pillow-exact resize + crop / flip / normalise on the GPU
 # -------------------------------------------------------------------------------------------------
@@ -653,7 +692,8 @@ class CustomSemanticKITTILssDataset:
 
 def collate(samples, device="cuda"):
     """Batch of pipeline outputs -> the detector's call signature: ``img_inputs = (left10, right10)`` with a leading
-    batch axis on every entry (what mmcv's collate + scatter produce upstream), ``gt_occ`` [B, X, Y, Z] int64."""
+    batch axis on every entry (what mmcv's collate + scatter produce upstream), ``gt_occ`` [B, X, Y, Z] int64; ``frustums_ids`` / ``frustums_class_dists`` / ``frustums_masks`` are stacked
+    when every sample carries them."""
     on_gpu = torch.device(device).type == "cuda"
 
     def put(t):
@@ -678,7 +718,11 @@ def collate(samples, device="cuda"):
             attach_host_inverses(cols[4], cols[3], host[0], host[1])
         views.append(tuple(cols))
     gt = put(torch.stack([torch.as_tensor(s["gt_occ"]).long() for s in samples]))
-    return dict(img_inputs=tuple(views), gt_occ=gt)
+    out = dict(img_inputs=tuple(views), gt_occ=gt)
+    for k in ("frustums_ids", "frustums_class_dists", "frustums_masks"):     # CreateRelationLabels' outputs, when every sample has them
+        if all(k in s for s in samples):
+            out[k] = put(torch.stack([torch.as_tensor(s[k]) for s in samples]))
+    return out
 
 
 @PIPELINES.register_module()

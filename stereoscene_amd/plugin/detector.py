@@ -61,7 +61,7 @@ class BEVDepthOccupancy(nn.Module):
         outs = self.pts_bbox_head(voxel_feats=voxel_feats, points=points_occ, img_metas=img_metas)
         return self.pts_bbox_head.loss(output_voxels=outs["output_voxels"], target_voxels=gt_occ,
                                        output_points=outs["output_points"], target_points=points_occ,
-                                       img_metas=img_metas)
+                                       img_metas=img_metas, **kwargs)       # DET:138-175: frustums_ids / _class_dists, ...
 
     def forward_train(self, points=None, img_metas=None, img_inputs=None, gt_occ=None, points_occ=None,
                       points_uv=None, **kwargs):
@@ -69,7 +69,7 @@ class BEVDepthOccupancy(nn.Module):
         losses = {}
         if not self.disable_loss_depth:
             losses["loss_depth"] = self.img_view_transformer.get_depth_loss(img_inputs[0][7], depth)   # DET:230
-        losses.update(self.forward_pts_train(voxel_feats, gt_occ, points_occ, img_metas))
+        losses.update(self.forward_pts_train(voxel_feats, gt_occ, points_occ, img_metas, **kwargs))
         return losses
 
     def simple_test(self, img_metas=None, img=None, rescale=False, points_occ=None, gt_occ=None, points_uv=None):

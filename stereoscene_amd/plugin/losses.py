@@ -195,8 +195,73 @@ def ohem_ce_loss(logits, gt_occ, class_weights, top_k=0.25):
     return ohem_ce_tensor(logits, gt_occ, class_weights.to(logits), top_k)
 
 
+def frustum_dist_tensor(logits, ids_or_masks, dists):
+    """compute_frustum_dist_loss (utils/semkitti.py:218-244) of logits that already sit on the frustum grid, from tensor ops on any
+    device and in the logits' dtype, without a read-back.  ``ids_or_masks``: the id volume [B,X,Y,Z] (integer; 255 = in no frustum)
+    or the reference's dense bool masks [B,F,X,Y,Z] (which may overlap); ``dists`` [B,F,C] class counts.  Per frustum, pooled
+    over the batch: cum = sum of the softmax over its voxels, t = counts / their sum, q = cum / its sum, the term
+    sum over t_c != 0 of t_c (log t_c - log q_c) (``KL_sep``); the mean over the frusta whose two sums are both > 0.  With no such
+    frustum the reference divides 0 / 0 (ZeroDivisionError); here the loss is 0 with a zero gradient."""
+    p = torch.softmax(logits, dim=1)
+    B, Cn = p.shape[:2]
+    F = dists.shape[1]
+    if ids_or_masks.dim() == 5:
+        cum = torch.einsum("bfn,bcn->fc", ids_or_masks.flatten(2).to(p.dtype), p.flatten(2))
+    else:
+        ids = ids_or_masks.flatten(1).long()
+        ids = torch.where(ids < F, ids, torch.full_like(ids, F))                   # row F collects the voxels of no frustum
+        cum = p.new_zeros(F + 1, Cn).index_add_(0, ids.reshape(-1), p.flatten(2).transpose(1, 2).reshape(-1, Cn))[:F]
+    cnt = dists.to(p.dtype).sum(0)
+    total_prob, total_cnt = cum.sum(1, keepdim=True), cnt.sum(1, keepdim=True)
+    counted = (total_prob > 0) & (total_cnt > 0)                                  # [F, 1]
+    one = torch.ones_like(total_prob)
+    t = cnt / torch.where(counted, total_cnt, one)
+    q = cum / torch.where(counted, total_prob, one)
+    use = counted & (t != 0)
+    term = torch.where(use, t * (torch.log(torch.where(use, t, one)) - torch.log(torch.where(use, q, one))), torch.zeros_like(t))
+    n = counted.sum().to(p.dtype)
+    return term.sum() / torch.where(n > 0, n, torch.ones_like(n))
+
+
+def frustum_dist_loss(logits, ids_or_masks, dists):
+    """Frustum-proportion voxel loss of the head (occhead.py:326-329): logits [B,C,d,h,w] are up-sampled trilinearly to the grid of
+    the ids [B,D,H,W] (or of the reference's dense masks [B,F,D,H,W], which are turned into ids when they are disjoint).  The fused
+    HIP path serves what ``functional.frustum_dist_supported`` accepts; everything else (other devices, dtypes, class counts or
+    ratios, overlapping masks, ``SSBEV_FRUSTUM_DIST=0``) runs ``frustum_dist_tensor``."""
+    from .. import functional as F
+    ids_or_masks = ids_or_masks.to(logits.device)                     # (the loader step's output may still live on the host)
+    if ids_or_masks.dim() == 5 and F.FRUSTUM_DIST and logits.is_cuda:
+        ids = F.frustum_ids_from_masks(ids_or_masks)
+        ids_or_masks = ids_or_masks if ids is None else ids
+    if ids_or_masks.dim() == 4 and F.FRUSTUM_DIST and F.frustum_dist_supported(logits, ids_or_masks.to(torch.uint8), dists):
+        return F.frustum_dist_loss(logits, ids_or_masks, dists)
+    grid = tuple(ids_or_masks.shape[-3:])
+    if tuple(logits.shape[-3:]) != grid:
+        if logits.is_cuda:
+            logits = F.upsample_trilinear(logits, grid)
+        else:                                                         # (the HIP up-sampling has no CPU form)
+            logits = TF.interpolate(logits, size=grid, mode="trilinear", align_corners=False)
+    return frustum_dist_tensor(logits, ids_or_masks, dists.detach().to(logits))
+
+
+def _frustum_term(logits, gt_occ, frustums):
+    """The frustum-proportion loss from the head's keyword arguments: ``frustums_ids`` (preferred) or ``frustums_masks``, and
+    ``frustums_class_dists``."""
+    if frustums is None or "frustums_class_dists" not in frustums:
+        raise KeyError("frustums_class_dists")
+    if frustums.get("frustums_ids") is not None:
+        vol = frustums["frustums_ids"]
+    elif frustums.get("frustums_masks") is not None:
+        vol = frustums["frustums_masks"]
+    else:
+        raise KeyError("frustums_ids")
+    if tuple(vol.shape[-3:]) != tuple(gt_occ.shape[-3:]):
+        raise ValueError(f"frustum_dist: the frustum grid {tuple(vol.shape[-3:])} is not the label grid {tuple(gt_occ.shape[-3:])}")
+    return frustum_dist_loss(logits, vol, frustums["frustums_class_dists"])
+
+
 def occ_losses_fused(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0, w_geo=1.0, compute_metric=False,
-                     w_lovasz=0.0, w_ohem=0.0, ohem_topk=0.25):
+                     w_lovasz=0.0, w_ohem=0.0, ohem_topk=0.25, w_fp=0.0, frustums=None):
     """Same losses / metric as ``occ_losses`` from the sums of the fused HIP epilogue (one pass over the coarse
     logits; the up-sampled logits, probabilities and one-hot volumes are never materialised)."""
     from .. import functional as F
@@ -217,6 +282,8 @@ def occ_losses_fused(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0
             out[f"loss_voxel_sem_ohem_{tag}"] = ohem_ce_loss(logits, gt_occ, class_weights, ohem_topk) * w_ohem
         if w_lovasz > 0:
             out[f"loss_voxel_lovasz_{tag}"] = lovasz_softmax_loss(logits, gt_occ) * w_lovasz
+        if w_fp > 0:
+            out[f"loss_voxel_fp_{tag}"] = _frustum_term(logits, gt_occ, frustums) * w_fp
         if compute_metric:
             out[f"sc_iou_{tag}"], out[f"ssc_miou_{tag}"] = iou.detach(), miou.detach()
         return out
@@ -243,6 +310,8 @@ def occ_losses_fused(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0
         out[f"loss_voxel_sem_ohem_{tag}"] = ohem_ce_loss(logits, gt_occ, class_weights, ohem_topk) * w_ohem
     if w_lovasz > 0:
         out[f"loss_voxel_lovasz_{tag}"] = lovasz_softmax_loss(logits, gt_occ) * w_lovasz
+    if w_fp > 0:
+        out[f"loss_voxel_fp_{tag}"] = _frustum_term(logits, gt_occ, frustums) * w_fp
     if compute_metric:
         with torch.no_grad():
             tp = conf[1:, 1:].sum()
@@ -257,11 +326,12 @@ def occ_losses_fused(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0
 
 
 def occ_losses(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0, w_geo=1.0, compute_metric=False, w_lovasz=0.0,
-               w_ohem=0.0, ohem_topk=0.25):
-    """occhead.py:291-361: trilinear upsample to the label grid, CE + sem_scal + geo_scal (+ OHEM CE, + Lovasz-softmax, + metric)."""
+               w_ohem=0.0, ohem_topk=0.25, w_fp=0.0, frustums=None):
+    """occhead.py:291-361: trilinear upsample to the label grid, CE + sem_scal + geo_scal (+ OHEM CE, + Lovasz-softmax, + the
+    frustum-proportion loss from ``frustums`` = the head's keyword arguments, + metric)."""
     if (logits.is_cuda and logits.shape[1] == 20 and all(o == 2 * i for o, i in zip(gt_occ.shape[-3:], logits.shape[-3:]))):
         return occ_losses_fused(logits, gt_occ, class_weights, tag, w_ce, w_sem, w_geo, compute_metric, w_lovasz, w_ohem,
-                                ohem_topk)
+                                ohem_topk, w_fp, frustums)
     if logits.shape[-3:] != gt_occ.shape[-3:]:
         from ..functional import upsample_trilinear
         logits = upsample_trilinear(logits, gt_occ.shape[-3:])
@@ -279,6 +349,8 @@ def occ_losses(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0, w_ge
         out[f"loss_voxel_sem_ohem_{tag}"] = ohem_ce_loss(logits, gt_occ, class_weights, ohem_topk) * w_ohem
     if w_lovasz > 0:
         out[f"loss_voxel_lovasz_{tag}"] = lovasz_softmax_loss(logits, gt_occ) * w_lovasz
+    if w_fp > 0:
+        out[f"loss_voxel_fp_{tag}"] = _frustum_term(logits, gt_occ, frustums) * w_fp
     if compute_metric:
         with torch.no_grad():
             tp, fp, fn, tpc, fpc, fnc = ssc_counts(logits.argmax(1), t)

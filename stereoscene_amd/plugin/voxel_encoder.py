@@ -123,7 +123,8 @@ class OccHead(nn.Module):
                  supervise_points=False, loss_weight_cfg=None, semkitti_loss_weight_cfg=None,
                  loss_voxel_prototype="cylinder3d", use_ohem_loss=False, use_sc_ohem_loss=False, ohem_topk=0.25,
                  conv_cfg=dict(type="Conv3d", bias=False), norm_cfg=dict(type="GN", num_groups=32, requires_grad=True),
-                 point_cloud_range=(-51.2, -51.2, -5.0, 51.2, 51.2, 3.0), with_cp=False, train_cfg=None, test_cfg=None):
+                 point_cloud_range=(-51.2, -51.2, -5.0, 51.2, 51.2, 3.0), with_cp=False, train_cfg=None, test_cfg=None,
+                 use_frustum_loss=False):
         super().__init__()
         if supervise_points or not semantic_kitti or not supervise_voxel:
             raise NotImplementedError("only the voxel-supervised SemanticKITTI head used by the config is built")
@@ -147,9 +148,15 @@ class OccHead(nn.Module):
         # a stream synchronisation right before the losses) without adding a state-dict key the reference does not have
         self.register_buffer("class_weights", L.semkitti_class_weights(), persistent=False)
         self.semkitti_loss_weight_cfg = semkitti_loss_weight_cfg or {}
-        for k in ("frustum_dist", "voxel_dice", "voxel_lga"):
+        for k in ("voxel_dice", "voxel_lga"):
             if self.semkitti_loss_weight_cfg.get(k, 0.0) > 0:
                 raise NotImplementedError(f"loss '{k}' is disabled in the reference config and not built")
+        # the frustum-proportion loss runs behind a constructor flag of this head (the reference has none): the weight alone
+        # does not switch it on, because it needs the loader's frustums_ids / frustums_class_dists in the call of loss()
+        self.use_frustum_loss = bool(use_frustum_loss)
+        if self.semkitti_loss_weight_cfg.get("frustum_dist", 0.0) > 0 and not self.use_frustum_loss:
+            raise NotImplementedError("loss 'frustum_dist' is disabled in the reference config: pass use_frustum_loss=True to "
+                                      "OccHead (and CreateRelationLabels' outputs to loss()) to compute it")
         # the OHEM cross entropy runs behind the reference's constructor flag: the weight alone does not switch it on
         self.use_ohem_loss, self.ohem_topk = bool(use_ohem_loss), float(ohem_topk)
         if not 0.0 < self.ohem_topk <= 1.0:
@@ -170,12 +177,13 @@ class OccHead(nn.Module):
         return L.occ_losses(output_voxels, target_voxels, self.class_weights.to(output_voxels), tag,
                             w.get("voxel_ce", 0.0), w.get("voxel_sem_scal", 0.0), w.get("voxel_geo_scal", 0.0),
                             compute_metric, w.get("voxel_lovasz", 0.0),
-                            w.get("voxel_ohem", 0.0) if self.use_ohem_loss else 0.0, self.ohem_topk)
+                            w.get("voxel_ohem", 0.0) if self.use_ohem_loss else 0.0, self.ohem_topk,
+                            w.get("frustum_dist", 0.0) if self.use_frustum_loss else 0.0, kwargs)
 
     def loss(self, output_voxels=None, target_voxels=None, output_points=None, target_points=None, img_metas=None,
              **kwargs):
         targets = target_voxels[:self.num_level] if type(target_voxels) is list else [target_voxels] * self.num_level
         out = {}
         for i, o in enumerate(output_voxels):
-            out.update(self.loss_voxel_single_semkitti(o, targets[i], tag=str(i), compute_metric=(i == 0)))
+            out.update(self.loss_voxel_single_semkitti(o, targets[i], tag=str(i), compute_metric=(i == 0), **kwargs))
         return out

@@ -233,6 +233,117 @@ def kitti_calibration(B, img_w, right=False):
     return rots, trans, intr, post_rots, post_trans, bda, calib
 
 
+def frustum_view(cfg, B=1, post=None, bda=None):
+    """The left view of ``kitti_calibration`` in the ``img_inputs`` layout with a (stride-0, all-zero) image of the config's
+    input size in slot 0: (imgs [B,1,3,H,W], rots, trans, intrins, post_rots, post_trans, bda).  ``post`` = (2x2, 2-vector)
+    and ``bda`` (3x3 or 4x4) replace the identity post transform / BEV matrix."""
+    H, W = cfg["input_size"]
+    rots, trans, intr, post_rots, post_trans, bda0, _ = kitti_calibration(B, W)
+    if post is not None:
+        post_rots, post_trans = post_rots.clone(), post_trans.clone()
+        post_rots[..., :2, :2] = torch.as_tensor(post[0], dtype=torch.float32)
+        post_trans[..., :2] = torch.as_tensor(post[1], dtype=torch.float32)
+    if bda is not None:
+        bda0 = torch.as_tensor(bda, dtype=torch.float32).unsqueeze(0).repeat(B, 1, 1)
+    return (torch.zeros(1).expand(B, 1, 3, H, W), rots, trans, intr, post_rots, post_trans, bda0)
+
+
+# Cases of the loader-step tests (tools/make_golden_frustum.py records the reference on them), all on CFG_T's grid (32, 32, 8)
+# and image size.  P: identity post transform, 3x3 identity BEV matrix, every voxel labelled.  Q: resize + crop + flip post
+# transform, a 4x4 BEV matrix (rotation about the centre of the range and a flip of y), ~10 % of the labels 255.  R: a yaw of the
+# BEV matrix that puts a good third of the grid behind the camera or outside the image.
+FRUSTUM_LABEL_CASES = ("P", "Q", "R")
+FRUSTUM_LABEL_SEED = {"P": 0, "Q": 0, "R": 0}     # bumped when the generator refuses a fixture (see its comparison rule)
+
+
+def frustum_label_case(name):
+    """(labels uint8 [32,32,8], the left view of ``frustum_view``, point-cloud range) of a loader case."""
+    cfg = CFG_T
+    shape = tuple(cfg["occ_size"])
+    tag = f"frustum_{name}{FRUSTUM_LABEL_SEED[name]}"
+    lab = hash_uniform(f"{tag}_lab", shape, 0.0, 20.0).long().clamp_(0, 19).to(torch.uint8)
+    r = torch.tensor(cfg["pc_range"], dtype=torch.float64)
+    centre = (r[:3] + r[3:]) / 2
+    post = bda = None
+    if name == "Q":
+        lab[hash_uniform(f"{tag}_ign", shape, 0.0, 1.0) < 0.1] = 255
+        s, W = 0.9375, cfg["input_size"][1]
+        post = ([[-s, 0.0], [0.0, s]], [W - 3.0 * s, -2.0 * s])          # resize by s, crop at (-8 s .. ), mirror about the width
+        ang = math.radians(7.0)
+        rot = torch.tensor([[math.cos(ang), -math.sin(ang), 0, 0], [math.sin(ang), math.cos(ang), 0, 0], [0, 0, 1, 0],
+                            [0, 0, 0, 1]], dtype=torch.float64)
+        norm, denorm = torch.eye(4, dtype=torch.float64), torch.eye(4, dtype=torch.float64)
+        norm[:3, 3], denorm[:3, 3] = -centre, centre
+        bda = denorm @ torch.diag(torch.tensor([1.0, -1.0, 1.0, 1.0], dtype=torch.float64)) @ rot @ norm
+    if name == "R":
+        ang = math.radians(75.0)
+        bda = torch.tensor([[math.cos(ang), -math.sin(ang), 0], [math.sin(ang), math.cos(ang), 0], [0, 0, 1]], dtype=torch.float64)
+    return lab, frustum_view(cfg, 1, post, bda), cfg["pc_range"]
+
+
+# Cases of the frustum-proportion loss tests (tools/make_golden_frustum.py records the reference on them): name -> (logits shape,
+# id grid, frusta).  A: x2, the ids of the loader rule on a 16 x 12 x 8 grid under two yawed cameras (most frusta empty: the skip
+# rule); B: same grid; C: ids drawn per voxel from 0..63 and 255 (every wave sees many ids), classes without a count that receive
+# probability, frustum 5 with voxels and an all-zero count row, frustum 9 with counts and no voxel; D: every id 255 (loss 0,
+# gradient 0; the reference raises ZeroDivisionError); E: A with the first frustum both samples see kept in sample 0 only and the
+# counts of the second taken from sample 1 only; F: x2, 16 frusta in slabs of whole frusta ALONG THE LAST AXIS, so every frustum
+# has voxels in each of the eight 8192-voxel workgroup tiles (eight partial rows per frustum); G: F's shape with two samples,
+# sixteen partial tables (more than the eight strided slices of the fold, whose loop runs twice); only G's scalars are recorded.
+FRUSTUM_CASES = {"A": ((2, 20, 8, 6, 4), (2, 16, 12, 8), 64), "B": ((1, 20, 16, 16, 8), (1, 16, 16, 8), 64),
+                 "C": ((1, 20, 16, 12, 8), (1, 16, 12, 8), 64), "D": ((2, 20, 8, 6, 4), (2, 16, 12, 8), 64),
+                 "E": ((2, 20, 8, 6, 4), (2, 16, 12, 8), 64), "F": ((1, 20, 16, 32, 16), (1, 32, 64, 32), 16),
+                 "G": ((2, 20, 16, 32, 16), (2, 32, 64, 32), 16)}
+
+
+def _frustum_counts(ids, lab, F):
+    """float [B, F, 20]: labelled voxels per sample, frustum and class."""
+    B = ids.shape[0]
+    out = torch.zeros(B, F * 20)
+    for b in range(B):
+        ok = (ids[b] != 255) & (lab[b] != 255)
+        out[b].index_add_(0, (ids[b].long() * 20 + lab[b].long())[ok], torch.ones(int(ok.sum())))
+    return out.view(B, F, 20)
+
+
+def frustum_case(name):
+    """(logits fp32 [B,20,d,h,w] ~ N(0, 2^2), ids uint8 [B,D,H,W], counts fp32 [B,F,20]) of FRUSTUM_CASES[name].  The counts are
+    those of hashed labels inside the ids' frusta (so the labelled mix differs from the predicted one), edited as the case says."""
+    coarse, fine, F = FRUSTUM_CASES[name]
+    src = "A" if name in "DE" else name
+    logits = hash_normal(f"frustum_{src}_x", coarse, 2.0)
+    lab = lovasz_labels(f"frustum_{src}", fine)
+    B = fine[0]
+    if src == "A":
+        from . import functional as Fn
+        ids = torch.stack([Fn.frustum_labels(torch.zeros(fine[1:], dtype=torch.uint8), frustum_view(CFG_T, 1, bda=torch.tensor(
+            [[math.cos(a), -math.sin(a), 0.0], [math.sin(a), math.cos(a), 0.0], [0.0, 0.0, 1.0]])), CFG_T["pc_range"])[0]
+            for a in (math.radians(100.0), math.radians(95.0))])
+    elif name == "B":
+        i = torch.arange(fine[1]).view(-1, 1, 1) // 2
+        j = torch.arange(fine[2]).view(1, -1, 1) // 2
+        ids = (i * 8 + j).expand(fine[1:]).clone().to(torch.uint8).unsqueeze(0)       # 2 x 2 columns of voxels, all 64 frusta
+        ids[hash_uniform("frustum_B_none", fine, 0.0, 1.0) < 0.2] = 255
+    elif name == "C":
+        ids = hash_uniform("frustum_C_ids", fine, 0.0, 65.0).long().clamp_(0, 64)
+        ids[ids == 9] = 10                                                            # frustum 9 holds no voxel
+        ids = torch.where(ids == 64, torch.full_like(ids, 255), ids).to(torch.uint8)
+    else:                                                                             # F, G: slabs of whole frusta along the last axis
+        ids = (torch.arange(fine[3]) // 2).view(1, 1, 1, -1).expand(fine).clone().to(torch.uint8)
+        ids[hash_uniform(f"frustum_{name}_none", fine, 0.0, 1.0) < 0.1] = 255
+    if name == "D":
+        ids = torch.full(fine, 255, dtype=torch.uint8)
+    if name == "E":
+        both = [f for f in range(F) if all(bool((ids[b] == f).any()) for b in range(B))]     # frusta both samples see
+        ids[1][ids[1] == both[0]] = 255
+    dists = _frustum_counts(ids, lab, F)
+    if name == "C":
+        dists[0, 5] = 0.0                                                             # voxels, no counts: skipped
+        dists[0, 9, 0], dists[0, 9, 4] = 7.0, 2.0                                     # counts, no voxel: skipped
+    if name == "E":
+        dists[0, both[1]] = 0.0
+    return logits, ids, dists
+
+
 def synthetic_sample(cfg, B=1, C_in=640, tag="s0", with_targets=True):
     """Image-neck outputs for both views + geometry + targets, all hash-generated.
 
