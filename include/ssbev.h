@@ -211,6 +211,24 @@ int ssbev_conv_kernel_class(const ssbev_conv_dims* d, int mode);
  * block (9).  Mode 2: the chunk length of wgrad_tapdh_kernel (2 x 2 blocks) when ssbev_conv_bwd_weight takes that kernel.
  * 0 in every other case.  The launchers call the same plan functions, so the answer is the launch's own. */
 int ssbev_conv_chunk_groups(const ssbev_conv_dims* d, int mode);
+/* Host-side plan query of the bf16 storage family (since ssbev_version() 113; no device work; csrc/conv_bf16.hip): the kernel,
+ * template instance and launch geometry ssbev_conv_fwd_bf16 (mode 0), ssbev_conv_bwd_data_bf16 (mode 1) and
+ * ssbev_conv_bwd_weight_bf16 (mode 2) use for these dims, from the plan functions the launchers themselves read.  Only the group
+ * of the reported kernel class is filled in, every other field is 0.  SSBEV_EINVAL for a NULL argument, a mode outside 0 .. 2
+ * and dims the entry point of that mode refuses (precision 0 / 1, channel counts, precision 3 in mode 2). */
+typedef struct {
+  int kernel;                     /* 16 .. 21, what ssbev_conv_kernel_class answers */
+  int mt, nt;                     /* 16: conv_gather16_kernel<MT, NT>, 32-voxel x 32-channel tiles per wave */
+  int bm, bn, bkc;                /* 21: conv_igemm16_kernel, workgroup tile (rows x columns) and source channels per stage */
+  int ntl, nth, ntw, ntn;         /* 19: conv_wide16_kernel<NTL>; tiles along h (16 rows), w (16 voxels), the output channels */
+  int nseg, gpc;                  /* 17: conv_tap16_kernel; 32-voxel w segments, rows per workgroup chunk */
+  int mq, mp, th, tw;             /* 18: wgrad16_kernel<MQ, MP, TH, TW> */
+  int chunk, nchunks;             /* 18: voxels per wave chunk, chunks (four per workgroup); 20: nchunks = tile chunks */
+  int narrow, tpc, ncqt;          /* 20: wgrad_ring16_kernel<NARROW>, 8 x 16 tiles per chunk, 32-channel Q tiles */
+  int64_t grid;                   /* workgroups of the main launch */
+  size_t workspace;               /* mode 2: bytes, what ssbev_conv_bwd_weight_workspace returns; else 0 */
+} ssbev_conv_bf16_plan;
+int ssbev_conv_bf16_plan_query(const ssbev_conv_dims* d, int mode, ssbev_conv_bf16_plan* out);
 
 /* 32 -> 1 / 2 / 4 channel 3x3x3 stride-1 "same" layers (the 32 -> 1 classifiers of the cost-volume stack,
  * ViewTransformerLSSVoxel.py:185-187, 239-241; mode 1: the data gradient of a 1 / 2 / 4 -> 32 layer) as one pass over the

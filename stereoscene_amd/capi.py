@@ -125,6 +125,12 @@ class Wino43DfPlan(C.Structure):
                 ("w_grid", C.c_int64), ("w_lds_bytes", C.c_size_t), ("w_workspace", C.c_size_t)]
 
 
+class ConvBf16Plan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("kernel", "mt", "nt", "bm", "bn", "bkc", "ntl", "nth", "ntw", "ntn", "nseg", "gpc",
+                                       "mq", "mp", "th", "tw", "chunk", "nchunks", "narrow", "tpc", "ncqt")] + \
+        [("grid", C.c_int64), ("workspace", C.c_size_t)]
+
+
 class JitterParams(C.Structure):
     _fields_ = [("flags", C.c_int), ("mode", C.c_int), ("delta", C.c_float), ("alpha", C.c_float), ("saturation", C.c_float),
                 ("hue", C.c_float), ("perm", C.c_int * 3)]
@@ -162,6 +168,7 @@ SIGNATURES = {
     "ssbev_conv_packed_weight_elems": (C.c_size_t, [C.POINTER(ConvDims)]),
     "ssbev_conv_kernel_class": (C.c_int, [C.POINTER(ConvDims), C.c_int]),
     "ssbev_conv_chunk_groups": (C.c_int, [C.POINTER(ConvDims), C.c_int]),
+    "ssbev_conv_bf16_plan_query": (C.c_int, [C.POINTER(ConvDims), C.c_int, C.POINTER(ConvBf16Plan)]),
     "ssbev_frustum_geometry": (C.c_int, [_P] * 9 + [C.POINTER(GeomDims), _P]),
     "ssbev_conv_pack_weight": (C.c_int, [_P, _P, C.POINTER(ConvDims), C.c_int, _P]),
     "ssbev_conv_thin_workspace": (C.c_size_t, [C.POINTER(ConvDims), C.c_int]),

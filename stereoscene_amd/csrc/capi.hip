@@ -29,7 +29,7 @@ const char* ssbev_env(const char* name) {
 }
 
 extern "C" {
-int ssbev_version(void) { return 112; /* 0.1.12: + ssbev_frustum_dist_*, ssbev_frustum_labels */ }
+int ssbev_version(void) { return 113; /* 0.1.13: + ssbev_conv_bf16_plan_query */ }
 const char* ssbev_build_arch(void) { return "gfx950"; }
 
 // Forget every switch read so far: the next use of a name reads the environment again.  (Switches that a launch helper folded

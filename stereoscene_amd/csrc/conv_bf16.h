@@ -14,6 +14,7 @@ bool storage_mode(const ssbev_conv_dims* d);                       // precision 
 bool dims_ok(const ssbev_conv_dims* d, int mode);                  // channel multiples the kernels need (mode 0 fwd, 1 dgrad, 2 wgrad)
 int kernel_class(const ssbev_conv_dims* d, int mode);              // 16 / 17 / 19 forward + data gradient kernels, 18 / 20 weight gradient (ssbev.h)
 int tap_chunk_groups(const ssbev_conv_dims* d, int mode);          // rows per workgroup chunk of the class-17 launch, else 0
+int plan_query(const ssbev_conv_dims* d, int mode, ssbev_conv_bf16_plan* out);   // ssbev_conv_bf16_plan_query (ssbev.h)
 size_t packed_elems(const ssbev_conv_dims* d);                     // in floats (the buffer holds bf16 operands)
 int pack(const float* w_src, float* w_packed, const ssbev_conv_dims* d, int mode, hipStream_t st);
 int forward(const void* x, const float* wp, const float* bias, void* y, const ssbev_conv_dims* d, hipStream_t st);

@@ -956,21 +956,30 @@ int wide16_ntl(const ssbev_conv_dims* d, int mode) {        // 0 = not applicabl
   return ntl;
 }
 
-template <int NTL, typename YT>
-int launch_wide16(const bf16_t* x, const bf16_t* wp, const float* bias, YT* y, const ssbev_conv_dims* d, int mode, hipStream_t st) {
+// the geometry launch_wide16<NTL> hands to conv_wide16_kernel<NTL> (ntl = wide16_ntl(d, mode)) and the workgroups of that
+// launch; shared with the host-side plan query (ssbev_bf16::plan_query)
+Wide16Geom plan_wide16(const ssbev_conv_dims* d, int mode, int ntl) {
   Wide16Geom g;
   g.B = d->B; g.D = d->Do; g.H = d->Ho; g.W = d->Wo;
   g.K = mode == 0 ? d->Cin : d->Cout;
   g.N = mode == 0 ? d->Cout : d->Cin;
   g.KP = pad16(g.K) / 16; g.NPad = pad32(g.N);
-  g.nth = (g.H + kW16Rows - 1) / kW16Rows; g.ntw = g.W / 16; g.ntn = g.N / (32 * NTL);
+  g.nth = (g.H + kW16Rows - 1) / kW16Rows; g.ntw = g.W / 16; g.ntn = g.N / (32 * ntl);
   g.relu = mode == 0 ? d->relu : 0;
   g.accumulate = d->accumulate;
   g.mirror = mode == 1 ? 1 : 0;
+  return g;
+}
+
+long wide16_blocks(const Wide16Geom& g) { return (long)g.B * g.D * g.nth * g.ntw * g.ntn; }
+
+template <int NTL, typename YT>
+int launch_wide16(const bf16_t* x, const bf16_t* wp, const float* bias, YT* y, const ssbev_conv_dims* d, int mode, hipStream_t st) {
+  const Wide16Geom g = plan_wide16(d, mode, NTL);
   auto kern = conv_wide16_kernel<NTL, YT>;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kW16RingB) != hipSuccess)
     return SSBEV_ELAUNCH;
-  const long blocks = (long)g.B * g.D * g.nth * g.ntw * g.ntn;
+  const long blocks = wide16_blocks(g);
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), kW16RingB, st, x, wp, mode == 0 ? bias : nullptr, y, g);
   return ssbev_launch_status();
 }
@@ -1277,8 +1286,11 @@ int launch_igemm16_t(const bf16_t* x, const bf16_t* wp, const float* bias, YT* y
   return ssbev_launch_status();
 }
 
-template <typename YT>
-int launch_igemm16(const bf16_t* x, const bf16_t* wp, const float* bias, YT* y, const Geom16& g, hipStream_t st, int nbatch = 1) {
+// the workgroup tile and stage depth launch_igemm16 runs a problem with, and the workgroups of that launch; shared with the
+// host-side plan query (ssbev_bf16::plan_query)
+struct Igemm16Plan { int bm, bn, bkc; long blocks; };
+
+Igemm16Plan plan_igemm16(const Geom16& g, int nbatch) {
   long Mtot = (long)g.B * g.Do * g.Ho * g.Wo;
   long classes = nbatch;
   if (g.form == 1) {
@@ -1298,6 +1310,17 @@ int launch_igemm16(const bf16_t* x, const bf16_t* wp, const float* bias, YT* y, 
   if (force) { bm = force / 1000; bn = force % 1000; }
   static const int bkc_force = ssbev_tune("SSBEV_IGEMM16_BKC") ? atoi(ssbev_tune("SSBEV_IGEMM16_BKC")) : 0;    // probing: 32 = 32-channel stages
   const bool k64 = g.Cin % 64 == 0 && bkc_force != 32;
+  Igemm16Plan p;
+  p.bm = bm; p.bn = bn; p.bkc = k64 ? 64 : 32;
+  p.blocks = (bm > 0 && bn > 0) ? ((Mtot + bm - 1) / bm) * ((g.Cout + bn - 1) / bn) * classes : 0;
+  return p;
+}
+
+template <typename YT>
+int launch_igemm16(const bf16_t* x, const bf16_t* wp, const float* bias, YT* y, const Geom16& g, hipStream_t st, int nbatch = 1) {
+  const Igemm16Plan pl = plan_igemm16(g, nbatch);
+  const int bm = pl.bm, bn = pl.bn;
+  const bool k64 = pl.bkc == 64;
 #define SSBEV_IG16(WN_, MW_) (k64 ? launch_igemm16_t<WN_, MW_, 2, 64, YT>(x, wp, bias, y, g, st, nbatch) \
                                   : launch_igemm16_t<WN_, MW_, 2, 32, YT>(x, wp, bias, y, g, st, nbatch))
   if (bm == 128 && bn == 128) return SSBEV_IG16(2, 2);
@@ -1312,9 +1335,9 @@ int launch_igemm16(const bf16_t* x, const bf16_t* wp, const float* bias, YT* y, 
   return SSBEV_EINVAL;
 }
 
-template <typename YT>
-int dispatch_gather16(const bf16_t* x, const bf16_t* wp, const float* bias, YT* y, const Geom16& g, int hint, hipStream_t st) {
-  if (conv_igemm16_applicable(g, hint)) return launch_igemm16(x, wp, bias, y, g, st);
+// 10 MT + NT of the conv_gather16_kernel<MT, NT> instance dispatch_gather16 runs (a hint that names no instance is refused
+// there); shared with the host-side plan query (ssbev_bf16::plan_query)
+int plan_gather16(const Geom16& g, int hint) {
   int mt, nt;
   if (hint >= 10) { mt = hint / 10; nt = hint % 10; }
   else {
@@ -1325,7 +1348,17 @@ int dispatch_gather16(const bf16_t* x, const bf16_t* wp, const float* bias, YT* 
     mt = gather_blocks(g, 2, nt) >= 160 ? 2 : 1;
     if (g.form == 1 && g.sd * g.sh * g.sw > 1) { mt = 1; nt = nt > 2 ? 2 : nt; }     // parity classes: short loops, small tiles
   }
-  switch (mt * 10 + nt) {
+  return mt * 10 + nt;
+}
+
+bool gather16_instance(int tiling) {
+  switch (tiling) { case 11: case 12: case 14: case 21: case 22: case 24: case 26: return true; default: return false; }
+}
+
+template <typename YT>
+int dispatch_gather16(const bf16_t* x, const bf16_t* wp, const float* bias, YT* y, const Geom16& g, int hint, hipStream_t st) {
+  if (conv_igemm16_applicable(g, hint)) return launch_igemm16(x, wp, bias, y, g, st);
+  switch (plan_gather16(g, hint)) {
     case 11: return launch_gather16<1, 1, YT>(x, wp, bias, y, g, st);
     case 12: return launch_gather16<1, 2, YT>(x, wp, bias, y, g, st);
     case 14: return launch_gather16<1, 4, YT>(x, wp, bias, y, g, st);
@@ -1361,13 +1394,14 @@ Tap16Geom plan_tap16(const ssbev_conv_dims* d, int mode) {
   return g;
 }
 
+long tap16_blocks(const Tap16Geom& g) { return (long)((g.NG + g.gpc - 1) / g.gpc) * g.nseg; }
+
 template <typename YT>
 int launch_tap16(const bf16_t* x, const float* wp, const float* bias, YT* y, const ssbev_conv_dims* d, int mode, hipStream_t st) {
   Tap16Geom g = plan_tap16(d, mode);
   g.has_bias = (mode == 0 && bias) ? 1 : 0;
-  const long nranges = (g.NG + g.gpc - 1) / g.gpc;
   auto kern = conv_tap16_kernel<YT>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(nranges * g.nseg)), dim3(256), kT16LdsBytes, st, x, reinterpret_cast<const uint4*>(wp),
+  hipLaunchKernelGGL(kern, dim3((unsigned)tap16_blocks(g)), dim3(256), kT16LdsBytes, st, x, reinterpret_cast<const uint4*>(wp),
                      bias, y, g);
   return ssbev_launch_status();
 }
@@ -1410,10 +1444,15 @@ Wg16Geom make_wg_geom(const ssbev_conv_dims* d) {
   return g;
 }
 
+// workgroups of wgrad16_kernel<MQ, MP, TH, TW>: [groups of four chunks][channel tiles][tap groups]
+long wg16_blocks(const Wg16Geom& g, const WgCfg16& c) {
+  const int ytiles = cdiv(g.Cq, 32 * c.MQ) * cdiv(g.Cp, 32 * c.MP);
+  return (long)cdiv(g.nchunks, 4) * ytiles * (g.kd * cdiv(g.kh, c.TH) * cdiv(g.kw, c.TW));
+}
+
 template <int MQ, int MP, int TH, int TW>
 int launch_wg16(const bf16_t* P, const bf16_t* Q, float* ws, const Wg16Geom& g, hipStream_t st) {
-  const int ytiles = cdiv(g.Cq, 32 * MQ) * cdiv(g.Cp, 32 * MP);
-  dim3 grid((unsigned)((long)cdiv(g.nchunks, 4) * ytiles * (g.kd * cdiv(g.kh, TH) * cdiv(g.kw, TW))));
+  dim3 grid((unsigned)wg16_blocks(g, WgCfg16{MQ, MP, TH, TW}));
   const size_t lds = (size_t)4 * (MP + MQ * TH * TW) * 1024;
   hipLaunchKernelGGL((wgrad16_kernel<MQ, MP, TH, TW>), grid, dim3(256), lds, st, P, Q, ws, g);
   return ssbev_launch_status();
@@ -1451,8 +1490,42 @@ WgRingGeom make_wr_geom(const ssbev_conv_dims* d) {
   return g;
 }
 
+bool wg_ring_narrow(const WgRingGeom& g) { return g.Cq <= 32 && g.Cp <= 32; }
+
+// workgroups of wgrad_ring16_kernel: narrow one per chunk; wide [chunk][group of four 32-channel P tiles][Q tile][kd]
+long wg_ring_blocks(const WgRingGeom& g) {
+  return wg_ring_narrow(g) ? (long)g.nchunks : (long)g.nchunks * g.ncqt * ((g.Cp + 127) / 128) * 3;
+}
+
+// the weight-gradient launch of ssbev_conv_bwd_weight_bf16: kernel, instance, geometry, workspace.  backward_weight,
+// wgrad_workspace and the host-side plan query (ssbev_bf16::plan_query) all read it
+struct Wgrad16Plan {
+  bool ring;
+  WgRingGeom r;                     // ring
+  Wg16Geom g;                       // !ring
+  WgCfg16 c;                        // !ring
+  long blocks;
+  size_t ws_bytes;
+};
+
+Wgrad16Plan plan_wgrad16(const ssbev_conv_dims* d) {
+  Wgrad16Plan p{};
+  p.ring = wg_ring_applicable(d);
+  if (p.ring) {
+    p.r = make_wr_geom(d);
+    p.blocks = wg_ring_blocks(p.r);
+    p.ws_bytes = (size_t)p.r.nchunks * 27 * p.r.Cq * p.r.Cp * sizeof(float);
+  } else {
+    p.g = make_wg_geom(d);
+    p.c = wg_cfg(p.g.Cp, p.g.Cq, p.g.kh, p.g.kw);
+    p.blocks = wg16_blocks(p.g, p.c);
+    p.ws_bytes = (size_t)p.g.nchunks * d->kd * d->kh * d->kw * p.g.Cp * p.g.Cq * sizeof(float);
+  }
+  return p;
+}
+
 int launch_wg_ring(const bf16_t* P, const bf16_t* Q, float* ws, WgRingGeom g, hipStream_t st) {
-  const bool narrow = g.Cq <= 32 && g.Cp <= 32;
+  const bool narrow = wg_ring_narrow(g);
   if (narrow) {
     const size_t lds = 3 * kWrQPlaneB + kWrRows * 16 * 64;
     hipLaunchKernelGGL(wgrad_ring16_kernel<true>, dim3(g.nchunks), dim3(256), lds, st, P, Q, ws, g);
@@ -1461,7 +1534,7 @@ int launch_wg_ring(const bf16_t* P, const bf16_t* Q, float* ws, WgRingGeom g, hi
     static const int xcd_order = ssbev_tune("SSBEV_WGRAD_RING_XCD") ? atoi(ssbev_tune("SSBEV_WGRAD_RING_XCD")) : 1;
     g.xcd_order = xcd_order;
     if (xcd_order)
-      hipLaunchKernelGGL(wgrad_ring16_kernel<false>, dim3(g.nchunks * g.ncqt * ((g.Cp + 127) / 128) * 3), dim3(256), lds, st, P, Q, ws, g);
+      hipLaunchKernelGGL(wgrad_ring16_kernel<false>, dim3((unsigned)wg_ring_blocks(g)), dim3(256), lds, st, P, Q, ws, g);
     else
       hipLaunchKernelGGL(wgrad_ring16_kernel<false>, dim3(g.nchunks, g.ncqt * ((g.Cp + 127) / 128), 3), dim3(256), lds, st, P, Q, ws, g);
   }
@@ -1550,30 +1623,25 @@ int backward_data(const void* gy, const float* wp, void* gx, const ssbev_conv_di
 }
 
 size_t wgrad_workspace(const ssbev_conv_dims* d) {
-  if (!dims_ok(d, 2)) return 0;
-  if (wg_ring_applicable(d)) {
-    const WgRingGeom r = make_wr_geom(d);
-    return (size_t)r.nchunks * 27 * r.Cq * r.Cp * sizeof(float);
-  }
-  const Wg16Geom g = make_wg_geom(d);
-  return (size_t)g.nchunks * d->kd * d->kh * d->kw * g.Cp * g.Cq * sizeof(float);
+  return dims_ok(d, 2) ? plan_wgrad16(d).ws_bytes : 0;
 }
 
 int backward_weight(const void* x, const void* gy, float* gw, const ssbev_conv_dims* d, void* ws, size_t ws_bytes, hipStream_t st) {
   if (!dims_ok(d, 2) || !x || !gy || !gw || !ws) return SSBEV_EINVAL;
-  if (ws_bytes < wgrad_workspace(d)) return SSBEV_EWORKSPACE;
+  const Wgrad16Plan pl = plan_wgrad16(d);
+  if (ws_bytes < pl.ws_bytes) return SSBEV_EWORKSPACE;
   float* partial = static_cast<float*>(ws);
-  if (wg_ring_applicable(d)) {
-    const WgRingGeom r = make_wr_geom(d);
+  if (pl.ring) {
+    const WgRingGeom& r = pl.r;
     const int rc = launch_wg_ring(static_cast<const bf16_t*>(gy), static_cast<const bf16_t*>(x), partial, r, st);
     if (rc != SSBEV_OK) return rc;
     ssbev_detail::wgrad_reduce(partial, gw, r.nchunks, 27, r.Cq, r.Cp, st);
     return ssbev_launch_status();
   }
-  const Wg16Geom g = make_wg_geom(d);
+  const Wg16Geom& g = pl.g;
   const bf16_t* P = static_cast<const bf16_t*>(d->transposed ? x : gy);
   const bf16_t* Q = static_cast<const bf16_t*>(d->transposed ? gy : x);
-  const WgCfg16 c = wg_cfg(g.Cp, g.Cq, g.kh, g.kw);
+  const WgCfg16& c = pl.c;
   int rc;
   if (c.TH == 3) rc = launch_wg16<1, 1, 3, 3>(P, Q, partial, g, st);
   else if (c.TW == 3) rc = launch_wg16<2, 2, 1, 3>(P, Q, partial, g, st);
@@ -1582,6 +1650,42 @@ int backward_weight(const void* x, const void* gy, float* gw, const ssbev_conv_d
   if (rc != SSBEV_OK) return rc;
   ssbev_detail::wgrad_reduce(partial, gw, g.nchunks, g.kd * g.kh * g.kw, g.Cq, g.Cp, st);
   return ssbev_launch_status();
+}
+
+// ssbev_conv_bf16_plan_query: the same predicates in the order run() / backward_weight() ask them, the same plan functions
+int plan_query(const ssbev_conv_dims* d, int mode, ssbev_conv_bf16_plan* out) {
+  if (!out || mode < 0 || mode > 2 || !dims_ok(d, mode)) return SSBEV_EINVAL;
+  ssbev_conv_bf16_plan p{};
+  if (mode == 2) {
+    const Wgrad16Plan w = plan_wgrad16(d);
+    p.kernel = w.ring ? 20 : 18;
+    if (w.ring) {
+      p.narrow = wg_ring_narrow(w.r) ? 1 : 0; p.tpc = w.r.tpc; p.nchunks = w.r.nchunks; p.ncqt = w.r.ncqt;
+    } else {
+      p.mq = w.c.MQ; p.mp = w.c.MP; p.th = w.c.TH; p.tw = w.c.TW; p.chunk = w.g.chunk; p.nchunks = w.g.nchunks;
+    }
+    p.grid = w.blocks;
+    p.workspace = w.ws_bytes;
+  } else if (tap16_applicable(d, mode)) {
+    const Tap16Geom g = plan_tap16(d, mode);
+    p.kernel = 17; p.nseg = g.nseg; p.gpc = g.gpc; p.grid = tap16_blocks(g);
+  } else if (const int ntl = wide16_ntl(d, mode)) {
+    const Wide16Geom g = plan_wide16(d, mode, ntl);
+    p.kernel = 19; p.ntl = ntl; p.nth = g.nth; p.ntw = g.ntw; p.ntn = g.ntn; p.grid = wide16_blocks(g);
+  } else {
+    const Geom16 g = make_geom(d, mode);
+    const int hint = d->tile_hint >= 10 ? d->tile_hint : 0;
+    if (conv_igemm16_applicable(g, hint)) {
+      const Igemm16Plan ig = plan_igemm16(g, 1);
+      p.kernel = 21; p.bm = ig.bm; p.bn = ig.bn; p.bkc = ig.bkc; p.grid = ig.blocks;
+    } else {
+      const int tiling = plan_gather16(g, hint);
+      if (!gather16_instance(tiling)) return SSBEV_EINVAL;       // (a tile_hint that names no instance: the launcher refuses it too)
+      p.kernel = 16; p.mt = tiling / 10; p.nt = tiling % 10; p.grid = gather_blocks(g, p.mt, p.nt);
+    }
+  }
+  *out = p;
+  return SSBEV_OK;
 }
 
 // ---- batched plain products on conv_igemm16_kernel (the Winograd frequency products of the bf16 storage mode) ----

@@ -4444,6 +4444,11 @@ int ssbev_conv_chunk_groups(const ssbev_conv_dims* d, int mode) {
   }
 }
 
+int ssbev_conv_bf16_plan_query(const ssbev_conv_dims* d, int mode, ssbev_conv_bf16_plan* out) {
+  if (!conv_dims_ok(d) || !ssbev_bf16::storage_mode(d)) return SSBEV_EINVAL;
+  return ssbev_bf16::plan_query(d, mode, out);
+}
+
 size_t ssbev_conv_packed_weight_elems(const ssbev_conv_dims* d) {
   if (!conv_dims_ok(d)) return 0;
   if (ssbev_bf16::storage_mode(d)) return ssbev_bf16::packed_elems(d);
