@@ -452,6 +452,42 @@ int ssbev_occ_loss_bwd(const float* logits, const uint8_t* label, const float* c
                        const float* coef, float* grad_logits, const ssbev_occloss_dims* d, void* ws,
                        size_t ws_bytes, ssbev_stream_t stream);
 
+/* Soft-Dice and LGA-weighted voxel losses of the head (since version 114; occhead.py:331-343, utils/dice_loss.py:36-66,
+ * utils/pal_loss.py).
+ *
+ * ssbev_occ_dice_tail: SoftDiceLossWithProb(p = 1) of the occupied probability 1 - p_0 against [t > 0] over the labelled voxels is
+ * a function of four sums of ssbev_occ_loss_fwd:  inter = (M - cnt[0]) - (sum_p[0] - nom[0]),
+ *   dice = 1 - (2 inter + smooth) / ((M - sum_p[0]) + (M - cnt[0]) + smooth).
+ * One small launch: out1 (float, device) = dice, jac41 (double, device) = its Jacobian row over (ce_num, sum_p[20], nom[20]) (only
+ * sum_p[0] and nom[0] are non-zero), which scaled by the incoming gradient is (part of) the `coef` of ssbev_occ_loss_bwd.
+ * SSBEV_EINVAL on a NULL pointer.
+ *
+ * ssbev_lga_weights: lga2 [B, X, Y, Z] uint8 = twice PositionAwareLoss.get_lga(label) (the sum over the 20 class masks of the
+ * 1-norm of torch.gradient), exact: per axis, with is(t) = [t < 20], an interior voxel adds is(t-) + is(t+) if its two neighbours
+ * differ (its own label does not enter), the first and the last voxel add 2 (is(a) + is(b)) [a != b] of the end pair (the
+ * one-sided difference); 0..12.  An ignored voxel (255) is in no class mask but is a neighbour that differs.  Neighbours never
+ * cross a sample or a row.  SSBEV_EINVAL: NULL pointers, B < 1, an axis shorter than 2 (torch.gradient raises there too),
+ * B X Y Z >= 2^31.
+ *
+ * ssbev_occ_lga_*: sum over the labelled voxels of w[t] (alpha + beta lga) (-log softmax(up(logits))[t]) over the sum of w[t], with
+ * the tensors of ssbev_occ_loss_fwd plus lga2 on the label grid.  One grid-stride pass over the fine voxels, per-wave float sums
+ * folded in wave order into per-workgroup double partials, a fixed-order fold: no float atomics, nothing read back, the same bits
+ * on every run.  numden (2 doubles, device) = numerator, denominator; loss (float, device) = num / den, and 0 when den == 0 (the
+ * reference divides 0 / 0).  Backward writes grad_out[0] / den * w[t] (alpha + beta lga) (p - onehot) per fine voxel (0 where
+ * ignored or den == 0) into the workspace and pulls it back to the coarse grid with ssbev_trilinear2x_bwd.
+ * SSBEV_EINVAL: NULL pointers, non-positive dims, C != 20, 20 x fine voxels >= 2^31;  SSBEV_EWORKSPACE: ws_bytes below the query.
+ * The queries answer 0 for refused dims. */
+int ssbev_occ_dice_tail(const double* sums, float smooth, float* out1, double* jac41, ssbev_stream_t stream);
+int ssbev_lga_weights(const uint8_t* label, uint8_t* lga2, int B, int X, int Y, int Z, ssbev_stream_t stream);
+size_t ssbev_occ_lga_workspace(const ssbev_occloss_dims* d);
+int ssbev_occ_lga_fwd(const float* logits, const uint8_t* label, const uint8_t* lga2, const float* class_weight, float alpha,
+                      float beta, double* numden, float* loss, const ssbev_occloss_dims* d, void* ws, size_t ws_bytes,
+                      ssbev_stream_t stream);
+size_t ssbev_occ_lga_bwd_workspace(const ssbev_occloss_dims* d);
+int ssbev_occ_lga_bwd(const float* logits, const uint8_t* label, const uint8_t* lga2, const float* class_weight, float alpha,
+                      float beta, const double* numden, const float* grad_out, float* grad_logits,
+                      const ssbev_occloss_dims* d, void* ws, size_t ws_bytes, ssbev_stream_t stream);
+
 /* ssbev_occ_predict (since version 103): the INFERENCE epilogue of the head in one pass over the coarse logits -- what the
  * reference does with F.interpolate (bevdepth_occupancy.py:293), torch.argmax + SSCMetrics (semantic_kitti_lss_dataset.py:
  * 231-287; apis/test.py:141-224) and the submission writer's argmax + learning_map_inv (apis/test.py:49-64), without the 168 MB

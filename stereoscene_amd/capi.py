@@ -321,6 +321,12 @@ SIGNATURES = {
     "ssbev_frustum_dist_bwd_workspace": (C.c_size_t, [C.POINTER(FrustumDims)]),
     "ssbev_frustum_dist_bwd": (C.c_int, [_P] * 5 + [C.POINTER(FrustumDims), _P, C.c_size_t, _P]),
     "ssbev_frustum_labels": (C.c_int, [_P] * 3 + [C.c_int] * 3 + [_P] + [C.c_int] * 3 + [_P]),
+    "ssbev_occ_dice_tail": (C.c_int, [_P, C.c_float, _P, _P, _P]),
+    "ssbev_lga_weights": (C.c_int, [_P, _P] + [C.c_int] * 4 + [_P]),
+    "ssbev_occ_lga_workspace": (C.c_size_t, [C.POINTER(UpsampleDims)]),
+    "ssbev_occ_lga_fwd": (C.c_int, [_P] * 4 + [C.c_float] * 2 + [_P] * 2 + [C.POINTER(UpsampleDims), _P, C.c_size_t, _P]),
+    "ssbev_occ_lga_bwd_workspace": (C.c_size_t, [C.POINTER(UpsampleDims)]),
+    "ssbev_occ_lga_bwd": (C.c_int, [_P] * 4 + [C.c_float] * 2 + [_P] * 3 + [C.POINTER(UpsampleDims), _P, C.c_size_t, _P]),
     "ssbev_grad_norm_workspace": (C.c_size_t, []),
     "ssbev_grad_norm": (C.c_int, [_P, C.c_int64, _P, _P, C.c_size_t, _P]),
     "ssbev_adamw_step": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.POINTER(AdamWCfg), _P, _P]),

@@ -2782,6 +2782,122 @@ def occ_loss_tail(diff, aux, w_ce, w_sem, w_geo):
     return _OccLossTail.apply(diff, aux, w_ce, w_sem, w_geo)
 
 
+class _OccDiceTail(torch.autograd.Function):
+    """(diff [41] f64, aux f64) from _OccLossSums -> the soft-Dice loss of the occupied probability (0-dim float),
+    ``ssbev_occ_dice_tail``: forward also returns the Jacobian row over ``diff``, backward scales it."""
+
+    @staticmethod
+    def forward(ctx, diff, aux, smooth):
+        lib = capi.load()
+        nd = diff.numel()
+        sums = torch.cat((diff[0:1], aux[0:2], diff[1:], aux[2:])).contiguous()      # the kernel's layout, as in _OccLossTail
+        assert sums.numel() == lib.ssbev_occ_loss_num_sums()
+        out = torch.empty(1, dtype=torch.float32, device=diff.device)
+        jac = torch.empty(nd, dtype=torch.float64, device=diff.device)
+        capi.check(lib.ssbev_occ_dice_tail(capi.ptr(sums), float(smooth), capi.ptr(out), capi.ptr(jac), capi.stream()),
+                   "ssbev_occ_dice_tail")
+        ctx.save_for_backward(jac)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (jac,) = ctx.saved_tensors
+        return jac * g.to(torch.float64), None, None
+
+
+def occ_dice_tail(diff, aux, smooth=1.0):
+    """Soft-Dice voxel loss (SoftDiceLossWithProb of ``1 - p_0`` against ``t > 0`` over the labelled voxels) from the sums of
+    ``occ_loss_sums``: one launch; its gradient joins the coefficient vector of ``ssbev_occ_loss_bwd``."""
+    return _OccDiceTail.apply(diff, aux, float(smooth))
+
+
+LGA = os.environ.get("SSBEV_LGA", "1") != "0"                # fused LGA-weighted cross entropy (0 = the tensor form: up-sampled volume + CE + label shifts)
+
+
+def lga_weights(label):
+    """Twice the local geometric anisotropy of ``PositionAwareLoss.get_lga`` for labels [B,X,Y,Z] (255 = ignore), uint8 in 0..12,
+    exact.  CUDA labels run ``ssbev_lga_weights``; CPU labels the same rule in tensor ops (``losses.lga_weights_tensor``).  An
+    axis shorter than 2 is a ``ValueError`` (``torch.gradient`` raises there too)."""
+    if label.dim() != 4 or min(label.shape[1:]) < 2:
+        raise ValueError(f"lga_weights: labels [B,X,Y,Z] with every axis >= 2 expected, got {tuple(label.shape)}")
+    if not label.is_cuda:
+        from .plugin import losses
+        return losses.lga_weights_tensor(label)
+    lib = capi.load()
+    lab = label.to(torch.uint8).contiguous()
+    out = torch.empty_like(lab)
+    B, X, Y, Z = lab.shape
+    with _span("occ_lga", 0.0, 2.0 * lab.numel(), "fwd   lga_weights"):
+        capi.check(lib.ssbev_lga_weights(capi.ptr(lab), capi.ptr(out), B, X, Y, Z, capi.stream()), "ssbev_lga_weights")
+    return out
+
+
+def occ_lga_supported(logits, gt_occ):
+    """The fused LGA-weighted cross entropy serves fp32 20-class logits on the GPU and a label grid of exactly twice their size."""
+    return (logits.is_cuda and logits.dim() == 5 and logits.shape[1] == 20 and logits.dtype == torch.float32
+            and gt_occ.dim() == 4 and gt_occ.shape[0] == logits.shape[0]
+            and tuple(int(v) for v in gt_occ.shape[1:]) == tuple(2 * int(v) for v in logits.shape[2:]))
+
+
+class _OccLga(torch.autograd.Function):
+    """logits [B,20,D,H,W] (coarse), label uint8 [B,2D,2H,2W], lga2 uint8 (``lga_weights``), class weights [20] -> the
+    LGA-weighted cross entropy (0-dim fp32), ``ssbev_occ_lga_fwd / _bwd``.  Forward keeps (num, den) on the device; nothing is read
+    back.  No gradient for the class weights (a buffer of the head)."""
+
+    @staticmethod
+    def forward(ctx, logits, label_u8, lga2, class_weight, alpha, beta):
+        lib = capi.load()
+        xcl = to_cl(_f32(logits, "occ_lga_loss"))
+        B, D, H, W, Cch = xcl.shape
+        d = capi.UpsampleDims(B, D, H, W, Cch)
+        dev = logits.device
+        lab, lga2 = label_u8.contiguous(), lga2.contiguous()
+        cw = class_weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if cw.numel() != Cch:
+            raise capi.SsbevError(f"occ_lga_loss: {Cch} class weights expected, got {cw.numel()}")
+        numden = torch.empty(2, dtype=torch.float64, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        ws = _ws(lib.ssbev_occ_lga_workspace(C.byref(d)), dev)
+        with _span("occ_lga", 0.0, 4.0 * xcl.numel() + 2.0 * lab.numel(), "fwd   occ_lga"):
+            capi.check(lib.ssbev_occ_lga_fwd(capi.ptr(xcl), capi.ptr(lab), capi.ptr(lga2), capi.ptr(cw), alpha, beta,
+                                             capi.ptr(numden), capi.ptr(loss), C.byref(d), capi.ptr(ws), ws.numel(),
+                                             capi.stream()), "ssbev_occ_lga_fwd")
+        ctx.save_for_backward(xcl, lab, lga2, cw, numden)
+        ctx.ab = (alpha, beta)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = capi.load()
+        xcl, lab, lga2, cw, numden = ctx.saved_tensors
+        B, D, H, W, Cch = xcl.shape
+        d = capi.UpsampleDims(B, D, H, W, Cch)
+        alpha, beta = ctx.ab
+        gl = g.to(torch.float32).reshape(1).contiguous()
+        gx = torch.empty_like(xcl)
+        ws = _ws(lib.ssbev_occ_lga_bwd_workspace(C.byref(d)), xcl.device)
+        with _span("occ_lga", 0.0, 8.0 * xcl.numel() + 2.0 * lab.numel() + 8.0 * 20 * lab.numel(), "bwd   occ_lga"):
+            capi.check(lib.ssbev_occ_lga_bwd(capi.ptr(xcl), capi.ptr(lab), capi.ptr(lga2), capi.ptr(cw), alpha, beta,
+                                             capi.ptr(numden), capi.ptr(gl), capi.ptr(gx), C.byref(d), capi.ptr(ws), ws.numel(),
+                                             capi.stream()), "ssbev_occ_lga_bwd")
+        return from_cl(gx), None, None, None, None, None
+
+
+def occ_lga_loss(logits, gt_occ, class_weights, alpha=1.0, beta=1.0):
+    """LGA-weighted cross entropy (PositionAwareLoss) of ``up(logits)`` against ``gt_occ`` (255 = ignore): the sum over the labelled
+    voxels of w[t] (alpha + beta lga) (-log p_t) over the sum of w[t]; 0 with a zero gradient when nothing is labelled; fp32, 0-dim.
+    Supported inputs (``occ_lga_supported``) with ``LGA`` on run on the fused HIP path; anything else on the tensor form of
+    plugin/losses.py after ``upsample_trilinear``."""
+    label_u8 = gt_occ.to(torch.uint8)
+    if LGA and occ_lga_supported(logits, label_u8):
+        return _OccLga.apply(logits, label_u8, lga_weights(label_u8), class_weights, float(alpha), float(beta))
+    from .plugin import losses
+    if not LGA and logits.is_cuda:
+        up = upsample_trilinear(logits, label_u8.shape[-3:])
+        return losses.pal_tensor(up, label_u8, class_weights.to(up), alpha, beta).float()
+    return losses.occ_lga_loss(logits, label_u8, class_weights, alpha, beta).float()
+
+
 # -------------------------------------------------------------------------------------------------
 # Image branch (SURVEY 8(f1)): depthwise conv with "same" padding, Swish, squeeze-excitation pieces
 # -------------------------------------------------------------------------------------------------

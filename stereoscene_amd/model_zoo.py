@@ -15,14 +15,16 @@ def image_branch_cfg(arch="b7"):
 
 
 def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False, loss_depth_type="bce", voxel_ohem=0.0,
-              ohem_topk=0.25, frustum_dist=0.0):
+              ohem_topk=0.25, frustum_dist=0.0, voxel_dice=0.0, voxel_lga=0.0):
     """Same structure and hyper-parameters as the reference config's ``model`` dict for the sizes in ``cfg`` (a
     synthetic.CFG_*).  ``image_branch=False`` (default, the benchmarked hot path a1-a16) leaves the 2-D
     image backbone/neck out: the detector then takes the image-neck features in place of raw images.  ``loss_depth_type``:
     "bce" (the reference config's value) or "kld".  ``voxel_ohem`` > 0 switches the head's OHEM cross entropy on with that
     weight (``semkitti_loss_weight_cfg.voxel_ohem``, ``use_ohem_loss=True``) and ``ohem_topk`` as the kept fraction.
     ``frustum_dist`` > 0 switches the head's frustum-proportion loss on with that weight
-    (``semkitti_loss_weight_cfg.frustum_dist``, ``use_frustum_loss=True``); the training call then needs ``frustums_ids`` / ``frustums_class_dists`` (pipelines.CreateRelationLabels)."""
+    (``semkitti_loss_weight_cfg.frustum_dist``, ``use_frustum_loss=True``); the training call then needs ``frustums_ids`` / ``frustums_class_dists`` (pipelines.CreateRelationLabels).
+    ``voxel_dice`` / ``voxel_lga`` > 0 switch the head's soft-Dice / LGA-weighted losses on with that weight
+    (``semkitti_loss_weight_cfg.voxel_dice`` / ``.voxel_lga``, ``use_dice_loss=True`` / ``use_lga_loss=True``)."""
     norm_cfg = dict(type="GN", num_groups=32, requires_grad=True)
     channels = [128, 256, 512]
     return dict(
@@ -41,9 +43,13 @@ def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False, 
                            sampling_img_feats=True, in_img_channels=640, soft_weights=True,
                            **(dict(use_ohem_loss=True, ohem_topk=ohem_topk) if voxel_ohem > 0 else {}),
                            **(dict(use_frustum_loss=True) if frustum_dist > 0 else {}),
+                           **(dict(use_dice_loss=True) if voxel_dice > 0 else {}),
+                           **(dict(use_lga_loss=True) if voxel_lga > 0 else {}),
                            semkitti_loss_weight_cfg={"voxel_ce": 1.0, "voxel_sem_scal": 1.0, "voxel_geo_scal": 1.0,
                                                      "voxel_ohem": float(voxel_ohem), "voxel_lovasz": 0.0,
-                                                     "frustum_dist": float(frustum_dist)}),
+                                                     "frustum_dist": float(frustum_dist),
+                                                     **({"voxel_dice": float(voxel_dice)} if voxel_dice > 0 else {}),
+                                                     **({"voxel_lga": float(voxel_lga)} if voxel_lga > 0 else {})}),
         train_cfg=dict(pts=None), test_cfg=dict(pts=None))
 
 

@@ -260,8 +260,97 @@ def _frustum_term(logits, gt_occ, frustums):
     return frustum_dist_loss(logits, vol, frustums["frustums_class_dists"])
 
 
+def dice_tensor(logits, target, smooth=1.0):
+    """Soft-Dice voxel loss of the head (occhead.py:331-336, SoftDiceLossWithProb of utils/dice_loss.py:36-66 with p = 1) of logits
+    that already sit on the label grid, from tensor ops on any device and in the logits' dtype: the occupied probability
+    ``softmax(logits)[:, 1:].sum(1)`` against ``target > 0`` over the labelled voxels,
+    1 - (2 sum(p t) + smooth) / (sum(p) + sum(t) + smooth).  Nothing labelled gives 1 - smooth / smooth = 0 with a zero gradient."""
+    p = torch.softmax(logits, dim=1)[:, 1:].sum(dim=1)
+    valid = target != 255
+    p = p[valid]
+    t = (target[valid] > 0).to(p.dtype)
+    return 1.0 - (2.0 * (p * t).sum() + smooth) / ((p + t).sum() + smooth)
+
+
+def dice_from_sums(diff, aux, smooth=1.0):
+    """``dice_tensor`` from the sums of the fused epilogue (``functional.occ_loss_sums``), in their dtype (float64): with
+    p_occ = 1 - p_0, sum(p_occ [t > 0]) = (M - cnt0) - (sum_p0 - nom0) (the ``inter`` of geo_scal), sum(p_occ) = M - sum_p0 and
+    sum([t > 0]) = M - cnt0.  The torch algebra behind ``SSBEV_OCC_TAIL=0``; ``functional.occ_dice_tail`` is the one-launch form."""
+    nc = (diff.numel() - 1) // 2
+    sum_p0, nom0 = diff[1], diff[1 + nc]
+    M, cnt0 = aux[1], aux[2]
+    occ_t = M - cnt0
+    inter = occ_t - (sum_p0 - nom0)
+    return 1.0 - (2.0 * inter + smooth) / ((M - sum_p0) + occ_t + smooth)
+
+
+def lga_weights_tensor(target):
+    """TWICE the local geometric anisotropy of ``PositionAwareLoss.get_lga`` (utils/pal_loss.py: the sum over the 20 class masks of
+    the 1-norm of ``torch.gradient``) for labels [B,X,Y,Z], uint8 in 0..12 and exact, from tensor ops on any device.  Per axis, with
+    is(t) = [t < 20]: an interior voxel adds is(t-) + is(t+) when its two neighbours differ (its own label does not enter); the
+    first and the last voxel add 2 (is(a) + is(b)) [a != b] of the end pair (the one-sided difference).  An ignored voxel (255) is
+    in no class mask but is a neighbour that differs.  An axis shorter than 2 is a ``ValueError`` (``torch.gradient`` raises too)."""
+    if target.dim() != 4 or min(target.shape[1:]) < 2:
+        raise ValueError(f"lga_weights_tensor: labels [B,X,Y,Z] with every axis >= 2 expected, got {tuple(target.shape)}")
+    t = target.to(torch.int16)
+    isc = (t < 20).to(torch.int16)
+    out = torch.zeros_like(t)
+
+    def pair(a, b, ia, ib):
+        return (a != b).to(torch.int16) * (ia + ib)
+    for dim in (1, 2, 3):
+        n = t.shape[dim]
+        first = 2 * pair(t.narrow(dim, 0, 1), t.narrow(dim, 1, 1), isc.narrow(dim, 0, 1), isc.narrow(dim, 1, 1))
+        last = 2 * pair(t.narrow(dim, n - 2, 1), t.narrow(dim, n - 1, 1), isc.narrow(dim, n - 2, 1), isc.narrow(dim, n - 1, 1))
+        parts = [first]
+        if n > 2:
+            parts.append(pair(t.narrow(dim, 0, n - 2), t.narrow(dim, 2, n - 2), isc.narrow(dim, 0, n - 2), isc.narrow(dim, 2, n - 2)))
+        parts.append(last)
+        out = out + torch.cat(parts, dim=dim)
+    return out.to(torch.uint8)
+
+
+def pal_tensor(logits, target, class_weights, alpha=1.0, beta=1.0):
+    """PositionAwareLoss (utils/pal_loss.py) of logits that already sit on the label grid, from tensor ops on any device and in the
+    logits' dtype, without a read-back: the class-weighted cross entropy per voxel times alpha + beta lga, summed over the labelled
+    voxels, over the sum of their class weights.  With nothing labelled the reference divides 0 / 0; here the loss is 0 with a
+    zero gradient."""
+    loss = TF.cross_entropy(logits, target.long(), weight=class_weights, ignore_index=255, reduction="none")
+    fac = alpha + beta * (0.5 * lga_weights_tensor(target).to(loss.dtype))
+    valid = target != 255
+    num = (loss * fac * valid.to(loss.dtype)).sum()
+    den = (class_weights[target.long().clamp(max=class_weights.numel() - 1)] * valid.to(class_weights.dtype)).sum().detach()
+    return num / torch.where(den > 0, den, torch.ones_like(den))
+
+
+def occ_lga_loss(logits, gt_occ, class_weights, alpha=1.0, beta=1.0):
+    """LGA-weighted voxel loss of the head (occhead.py:338-343): logits [B,C,d,h,w] are up-sampled trilinearly to the grid of
+    ``gt_occ`` [B,D,H,W].  The fused HIP path serves what ``functional.occ_lga_supported`` accepts; everything else (other devices,
+    dtypes, class counts or ratios, ``SSBEV_LGA=0``) runs ``pal_tensor``."""
+    from .. import functional as F
+    if F.LGA and F.occ_lga_supported(logits, gt_occ):
+        return F.occ_lga_loss(logits, gt_occ, class_weights, alpha, beta)
+    if logits.shape[-3:] != gt_occ.shape[-3:]:
+        if logits.is_cuda:
+            logits = F.upsample_trilinear(logits, gt_occ.shape[-3:])
+        else:                                                         # (the HIP up-sampling has no CPU form)
+            logits = TF.interpolate(logits, size=tuple(gt_occ.shape[-3:]), mode="trilinear", align_corners=False)
+    return pal_tensor(logits, gt_occ, class_weights.to(logits), alpha, beta)
+
+
+def _dice_term(logits, gt_occ):
+    """The soft-Dice loss outside the fused epilogue: up-sample, then ``dice_tensor``."""
+    if logits.shape[-3:] != gt_occ.shape[-3:]:
+        if logits.is_cuda:
+            from ..functional import upsample_trilinear
+            logits = upsample_trilinear(logits, gt_occ.shape[-3:])
+        else:
+            logits = TF.interpolate(logits, size=tuple(gt_occ.shape[-3:]), mode="trilinear", align_corners=False)
+    return dice_tensor(logits, gt_occ)
+
+
 def occ_losses_fused(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0, w_geo=1.0, compute_metric=False,
-                     w_lovasz=0.0, w_ohem=0.0, ohem_topk=0.25, w_fp=0.0, frustums=None):
+                     w_lovasz=0.0, w_ohem=0.0, ohem_topk=0.25, w_fp=0.0, frustums=None, w_dice=0.0, w_lga=0.0):
     """Same losses / metric as ``occ_losses`` from the sums of the fused HIP epilogue (one pass over the coarse
     logits; the up-sampled logits, probabilities and one-hot volumes are never materialised)."""
     from .. import functional as F
@@ -284,6 +373,10 @@ def occ_losses_fused(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0
             out[f"loss_voxel_lovasz_{tag}"] = lovasz_softmax_loss(logits, gt_occ) * w_lovasz
         if w_fp > 0:
             out[f"loss_voxel_fp_{tag}"] = _frustum_term(logits, gt_occ, frustums) * w_fp
+        if w_dice > 0:
+            out[f"loss_voxel_dice_{tag}"] = F.occ_dice_tail(diff, aux) * w_dice
+        if w_lga > 0:
+            out[f"loss_voxel_lga_{tag}"] = occ_lga_loss(logits, gt_occ, class_weights) * w_lga
         if compute_metric:
             out[f"sc_iou_{tag}"], out[f"ssc_miou_{tag}"] = iou.detach(), miou.detach()
         return out
@@ -312,6 +405,10 @@ def occ_losses_fused(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0
         out[f"loss_voxel_lovasz_{tag}"] = lovasz_softmax_loss(logits, gt_occ) * w_lovasz
     if w_fp > 0:
         out[f"loss_voxel_fp_{tag}"] = _frustum_term(logits, gt_occ, frustums) * w_fp
+    if w_dice > 0:
+        out[f"loss_voxel_dice_{tag}"] = dice_from_sums(diff, aux).float() * w_dice
+    if w_lga > 0:
+        out[f"loss_voxel_lga_{tag}"] = occ_lga_loss(logits, gt_occ, class_weights) * w_lga
     if compute_metric:
         with torch.no_grad():
             tp = conf[1:, 1:].sum()
@@ -326,12 +423,12 @@ def occ_losses_fused(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0
 
 
 def occ_losses(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0, w_geo=1.0, compute_metric=False, w_lovasz=0.0,
-               w_ohem=0.0, ohem_topk=0.25, w_fp=0.0, frustums=None):
+               w_ohem=0.0, ohem_topk=0.25, w_fp=0.0, frustums=None, w_dice=0.0, w_lga=0.0):
     """occhead.py:291-361: trilinear upsample to the label grid, CE + sem_scal + geo_scal (+ OHEM CE, + Lovasz-softmax, + the
-    frustum-proportion loss from ``frustums`` = the head's keyword arguments, + metric)."""
+    frustum-proportion loss from ``frustums`` = the head's keyword arguments, + soft Dice, + the LGA-weighted CE, + metric)."""
     if (logits.is_cuda and logits.shape[1] == 20 and all(o == 2 * i for o, i in zip(gt_occ.shape[-3:], logits.shape[-3:]))):
         return occ_losses_fused(logits, gt_occ, class_weights, tag, w_ce, w_sem, w_geo, compute_metric, w_lovasz, w_ohem,
-                                ohem_topk, w_fp, frustums)
+                                ohem_topk, w_fp, frustums, w_dice, w_lga)
     if logits.shape[-3:] != gt_occ.shape[-3:]:
         from ..functional import upsample_trilinear
         logits = upsample_trilinear(logits, gt_occ.shape[-3:])
@@ -351,6 +448,10 @@ def occ_losses(logits, gt_occ, class_weights, tag="0", w_ce=1.0, w_sem=1.0, w_ge
         out[f"loss_voxel_lovasz_{tag}"] = lovasz_softmax_loss(logits, gt_occ) * w_lovasz
     if w_fp > 0:
         out[f"loss_voxel_fp_{tag}"] = _frustum_term(logits, gt_occ, frustums) * w_fp
+    if w_dice > 0:
+        out[f"loss_voxel_dice_{tag}"] = _dice_term(logits, gt_occ) * w_dice
+    if w_lga > 0:
+        out[f"loss_voxel_lga_{tag}"] = occ_lga_loss(logits, gt_occ, class_weights) * w_lga
     if compute_metric:
         with torch.no_grad():
             tp, fp, fn, tpc, fpc, fnc = ssc_counts(logits.argmax(1), t)

@@ -124,7 +124,7 @@ class OccHead(nn.Module):
                  loss_voxel_prototype="cylinder3d", use_ohem_loss=False, use_sc_ohem_loss=False, ohem_topk=0.25,
                  conv_cfg=dict(type="Conv3d", bias=False), norm_cfg=dict(type="GN", num_groups=32, requires_grad=True),
                  point_cloud_range=(-51.2, -51.2, -5.0, 51.2, 51.2, 3.0), with_cp=False, train_cfg=None, test_cfg=None,
-                 use_frustum_loss=False):
+                 use_frustum_loss=False, use_dice_loss=False, use_lga_loss=False):
         super().__init__()
         if supervise_points or not semantic_kitti or not supervise_voxel:
             raise NotImplementedError("only the voxel-supervised SemanticKITTI head used by the config is built")
@@ -148,9 +148,13 @@ class OccHead(nn.Module):
         # a stream synchronisation right before the losses) without adding a state-dict key the reference does not have
         self.register_buffer("class_weights", L.semkitti_class_weights(), persistent=False)
         self.semkitti_loss_weight_cfg = semkitti_loss_weight_cfg or {}
-        for k in ("voxel_dice", "voxel_lga"):
-            if self.semkitti_loss_weight_cfg.get(k, 0.0) > 0:
-                raise NotImplementedError(f"loss '{k}' is disabled in the reference config and not built")
+        # the soft-Dice and the LGA-weighted losses run behind constructor flags of this head (the reference has none): the weight
+        # alone does not switch them on; alpha = beta = 1 as in the reference's PositionAwareLoss(num_class=out_channel)
+        self.use_dice_loss, self.use_lga_loss = bool(use_dice_loss), bool(use_lga_loss)
+        for k, flag, on in (("voxel_dice", "use_dice_loss", self.use_dice_loss), ("voxel_lga", "use_lga_loss", self.use_lga_loss)):
+            if self.semkitti_loss_weight_cfg.get(k, 0.0) > 0 and not on:
+                raise NotImplementedError(f"loss '{k}' is disabled in the reference config: pass {flag}=True to OccHead to "
+                                          "compute it")
         # the frustum-proportion loss runs behind a constructor flag of this head (the reference has none): the weight alone
         # does not switch it on, because it needs the loader's frustums_ids / frustums_class_dists in the call of loss()
         self.use_frustum_loss = bool(use_frustum_loss)
@@ -178,7 +182,9 @@ class OccHead(nn.Module):
                             w.get("voxel_ce", 0.0), w.get("voxel_sem_scal", 0.0), w.get("voxel_geo_scal", 0.0),
                             compute_metric, w.get("voxel_lovasz", 0.0),
                             w.get("voxel_ohem", 0.0) if self.use_ohem_loss else 0.0, self.ohem_topk,
-                            w.get("frustum_dist", 0.0) if self.use_frustum_loss else 0.0, kwargs)
+                            w.get("frustum_dist", 0.0) if self.use_frustum_loss else 0.0, kwargs,
+                            w.get("voxel_dice", 0.0) if self.use_dice_loss else 0.0,
+                            w.get("voxel_lga", 0.0) if self.use_lga_loss else 0.0)
 
     def loss(self, output_voxels=None, target_voxels=None, output_points=None, target_points=None, img_metas=None,
              **kwargs):

@@ -105,6 +105,38 @@ def ohem_case(name):
     return logits, lab, top_k
 
 
+# Cases of the soft-Dice / LGA-weighted loss tests (tools/make_golden_dice_lga.py records the reference on them): name -> (logits
+# shape, label grid).  A B C G: the Lovasz cases' tensors (A two samples; B many workgroups; C the logits already on the label grid
+# = the tensor-form route; G fewer voxels than a wave).  K: blocky labels, a hashed 3-class 8x6x4 volume repeated 2x2x2 (9 % of the
+# voxels have lga = 0), sample 0's first two planes ignored, and the last plane of sample 0 differs from the first plane of sample 1 (a
+# kernel that reads across the sample boundary gets other weights).  L: coarse 1x1x1 -> 2x2x2, every voxel is first-or-last on
+# every axis.  E: nothing labelled.  N: A without a voxel of class 0 (cnt0 = 0).  Z: A's labels, all-zero logits.
+DICE_LGA_CASES = {"A": LOVASZ_CASES["A"], "B": LOVASZ_CASES["B"], "C": LOVASZ_CASES["C"], "G": LOVASZ_CASES["G"],
+                  "K": ((2, 20, 8, 6, 4), (2, 16, 12, 8)), "L": ((1, 20, 1, 1, 1), (1, 2, 2, 2)),
+                  "E": LOVASZ_CASES["E"], "N": LOVASZ_CASES["A"], "Z": LOVASZ_CASES["A"]}
+
+
+def dice_lga_case(name):
+    """(logits fp32 [B,20,d,h,w] ~ N(0, 2^2), labels uint8 [B,D,H,W]) of DICE_LGA_CASES[name]."""
+    coarse, fine = DICE_LGA_CASES[name]
+    if name in "ABCGE":
+        return lovasz_case(name)
+    if name in "NZ":
+        logits, lab = lovasz_case("A")
+        if name == "N":
+            lab = torch.where(lab == 0, torch.full_like(lab, 9), lab)
+        return (torch.zeros(coarse) if name == "Z" else logits), lab
+    logits = hash_normal(f"dice_lga_{name}_x", coarse, 2.0)
+    if name == "L":
+        lab = torch.tensor([0, 5, 5, 255, 9, 9, 0, 13], dtype=torch.uint8).view(fine)
+        return logits, lab
+    classes = torch.tensor([0, 9, 15], dtype=torch.uint8)                     # K
+    small = classes[(hash_uniform("dice_lga_K_cls", (2, 8, 6, 4), 0.0, 1.0) * 3).long().clamp_(max=2)]
+    lab = small.repeat_interleave(2, 1).repeat_interleave(2, 2).repeat_interleave(2, 3).contiguous()
+    lab[0, :2] = 255
+    return logits, lab
+
+
 # Cases of the Gaussian KL depth-loss tests (tools/make_golden_depth_kld.py records the reference on them): name -> (gt_depths
 # shape [B, N, H, W], ds, dbound, units, density of LiDAR returns, their value range).  A: the reference grid (D = 112), 30 feature
 # pixels, blocks with 0 / 1 / many returns and the planted edge depths of DEPTH_KLD_PLANTS; B: D = 13 (no multiple of the
