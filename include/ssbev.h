@@ -721,6 +721,28 @@ int ssbev_depth_kld_bwd(const float* depth_pred, const float* grad_loss, const f
                         int fW, int ds, double d0, double d1, double dd, float sigma, float edge_scale, float weight, const void* ws,
                         size_t ws_bytes, ssbev_stream_t stream);
 
+/* Image-view segmentation loss (since ssbev_version() 115; ViewTransformerLSSVoxel.py:418-430 get_seg_loss: F.interpolate of the
+ * head's logits to the label map (nearest) + CrossEntropyLoss(weight, ignore_index=0)), without the up-sampled tensor.
+ *   logits   [BN, K, h, w] fp32, contiguous (2 <= K <= 32);  labels [BN, H, W] fp32 (h <= H, w <= W);  class_w [K] fp32
+ * Image pixel (y, x) reads the logits of cell (min(floor(y * s_h), h - 1), min(floor(x * s_w), w - 1)), s_h = (float)h / H and
+ * s_w = (float)w / W in fp32: torch's `nearest` rule.  The pixels of a cell form a rectangle; the rectangles tile the image.
+ * A pixel is valid when its label, truncated towards zero (the reference's .long()), lies in [1, K).  0 is the reference's
+ * ignore_index; a NaN and every value outside [0, K) are ignored as well and never index memory (the reference raises on them).
+ *   num = sum over valid pixels p of class_w[l_p] (lse(logits[:, cell(p)]) - logits[l_p, cell(p)]),  den = sum of class_w[l_p]
+ *   loss_out[0] = weight * (num / den); without a valid pixel loss_out[0] = 0 and the gradient is all zero (the reference: NaN).
+ * _fwd: one wavefront per cell counts the labels of its rectangle into K bins held in registers (lane c keeps bin c), takes one
+ * max-subtracted log-sum-exp and writes the cell's (num, den) in double; a second launch folds the cells in a fixed order (no
+ * atomics: the same bits every run).  The workspace keeps (num, den), the partials and the K counts of every cell; _bwd takes
+ * the SAME workspace (it reads the counts and den, not the labels) and writes every element of grad_logits exactly once:
+ *   grad_logits[c, cell] = grad_loss[0] * weight / den * (softmax_c * den_cell - n_c class_w[c]),  exactly 0 for a cell without
+ * a valid pixel.  SSBEV_EINVAL (before any device work) for a NULL pointer, K outside 2 .. 32, a non-positive dim, h > H, w > W,
+ * BN h w >= 2^24, and in _fwd for ws_bytes below the query, which answers 0 for refused dims. */
+size_t ssbev_imgseg_ce_workspace(int BN, int h, int w);
+int ssbev_imgseg_ce_fwd(const float* logits, const float* labels, const float* class_w, int BN, int K, int h, int w, int H, int W,
+                        float weight, float* loss_out, void* ws, size_t ws_bytes, ssbev_stream_t stream);
+int ssbev_imgseg_ce_bwd(const float* logits, const float* labels, const float* class_w, const float* grad_loss, int BN, int K,
+                        int h, int w, int H, int W, float weight, float* grad_logits, const void* ws, ssbev_stream_t stream);
+
 size_t ssbev_lidar_depth_workspace(int H, int W);
 int ssbev_lidar_depth_map(const float* points, int n_points, const float* cam, const float* labels, float* uvd,
                           unsigned char* valid, float* depth, float* seg, int H, int W, void* ws, size_t ws_bytes,

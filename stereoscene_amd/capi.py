@@ -219,6 +219,9 @@ SIGNATURES = {
     "ssbev_depth_kld_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "ssbev_depth_kld_fwd": (C.c_int, [_P, _P, _P] + [C.c_int] * 5 + [C.c_double] * 3 + [C.c_float] * 3 + [_P, C.c_size_t, _P]),
     "ssbev_depth_kld_bwd": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [C.c_double] * 3 + [C.c_float] * 3 + [_P, C.c_size_t, _P]),
+    "ssbev_imgseg_ce_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "ssbev_imgseg_ce_fwd": (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [C.c_float, _P, _P, C.c_size_t, _P]),
+    "ssbev_imgseg_ce_bwd": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, _P, _P, _P]),
     "ssbev_lidar_depth_workspace": (C.c_size_t, [C.c_int, C.c_int]),
     "ssbev_lidar_depth_map": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_size_t, _P]),
     "ssbev_dwconv2d_fwd": (C.c_int, [_P, _P, _P, C.POINTER(DwDims), _P]),

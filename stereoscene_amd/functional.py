@@ -2742,6 +2742,101 @@ def depth_kld_loss(gt_depths, depth_pred, ds, dbound, weight, std=0.5, units="re
     return depth_kld_loss_tensor(gt_depths, depth_pred, ds, dbound, weight, std, units)
 
 
+IMGSEG = os.environ.get("SSBEV_IMGSEG", "1") != "0"          # fused image-view segmentation loss (0 = the tensor expression below)
+IMGSEG_MAX_CLASSES = 32
+
+
+def imgseg_nearest_index(n_in, n_out):
+    """int64 [n_out]: the source index ``F.interpolate(mode="nearest")`` reads for every destination index when ``n_in`` entries
+    are resized to ``n_out``: min(floor(i * s), n_in - 1) with s = (float)n_in / n_out and the product in fp32 -- the rule
+    ``ssbev_imgseg_ce_fwd`` derives its pixel rectangles from."""
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"sizes must be positive, got {n_in}, {n_out}")
+    s = torch.tensor(float(n_in), dtype=torch.float32) / torch.tensor(float(n_out), dtype=torch.float32)
+    return torch.floor(torch.arange(n_out, dtype=torch.float32) * s).long().clamp_(max=n_in - 1)
+
+
+def _imgseg_labels(seg_labels, K):
+    """int64 labels with everything outside [1, K) sent to 0 (= ignored); floating labels are truncated as ``.long()`` does."""
+    lab = seg_labels
+    if lab.is_floating_point():
+        lab = torch.where(torch.isfinite(lab), lab, torch.zeros_like(lab))
+    lab = lab.long()
+    return torch.where((lab >= 1) & (lab < K), lab, torch.zeros_like(lab))
+
+
+class _ImgSegCe(torch.autograd.Function):
+    """weight * class-weighted cross entropy of the nearest-up-sampled logits against the label map, ignore_index 0 (VT:418-430),
+    ``ssbev_imgseg_ce_fwd / _bwd``: logits fp32 [BN, K, h, w] contiguous, labels fp32 [BN, H, W], class weights fp32 [K] -> 0-dim
+    loss.  The [BN, K, H, W] tensor is never formed and nothing is read back to the host."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, class_w, weight):
+        lib = capi.load()
+        BN, K, h, w = logits.shape
+        H, W = labels.shape[1:]
+        args = (BN, K, h, w, H, W, float(weight))
+        ws = torch.empty(lib.ssbev_imgseg_ce_workspace(BN, h, w), dtype=torch.uint8, device=logits.device)   # kept for backward
+        out = torch.empty(1, dtype=torch.float32, device=logits.device)
+        capi.check(lib.ssbev_imgseg_ce_fwd(capi.ptr(logits), capi.ptr(labels), capi.ptr(class_w), *args, capi.ptr(out),
+                                           capi.ptr(ws), ws.numel(), capi.stream()), "ssbev_imgseg_ce_fwd")
+        ctx.save_for_backward(logits, labels, class_w, ws)
+        ctx.args = args
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = capi.load()
+        logits, labels, class_w, ws = ctx.saved_tensors
+        gx = torch.empty_like(logits)
+        gl = g.to(torch.float32).reshape(1).contiguous()
+        capi.check(lib.ssbev_imgseg_ce_bwd(capi.ptr(logits), capi.ptr(labels), capi.ptr(class_w), capi.ptr(gl), *ctx.args,
+                                           capi.ptr(gx), capi.ptr(ws), capi.stream()), "ssbev_imgseg_ce_bwd")
+        return gx, None, None, None
+
+
+def _imgseg_check(seg_logits, seg_labels, class_weights):
+    if seg_logits.dim() != 4 or seg_labels.dim() != 3 or seg_labels.shape[0] != seg_logits.shape[0]:
+        raise ValueError(f"logits [BN, K, h, w] and labels [BN, H, W] expected, got {tuple(seg_logits.shape)}, "
+                         f"{tuple(seg_labels.shape)}")
+    K = seg_logits.shape[1]
+    if not 2 <= K <= IMGSEG_MAX_CLASSES or class_weights.numel() != K:
+        raise ValueError(f"2 .. {IMGSEG_MAX_CLASSES} classes with one weight each expected, got {K} and {class_weights.numel()}")
+
+
+def imgseg_loss_tensor(seg_logits, seg_labels, class_weights, weight=1.0):
+    """The image-view segmentation loss in ATen ops, on any device (fp32; float64 when ``seg_logits`` is float64): the
+    reference's lines (VT:418-430) -- ``F.interpolate`` (nearest) of the logits to the label map, then the class-weighted
+    cross entropy with ``ignore_index=0`` -- as weighted sum over weight sum, so that no valid pixel gives 0 with a zero gradient
+    instead of the reference's 0 / 0.  Labels outside [0, K) are ignored (the reference raises on them)."""
+    _imgseg_check(seg_logits, seg_labels, class_weights)
+    dt = torch.float64 if seg_logits.dtype == torch.float64 else torch.float32
+    x = seg_logits.to(dt)
+    lab = _imgseg_labels(seg_labels, x.shape[1])
+    if x.shape[-2:] != lab.shape[-2:]:
+        x = torch.nn.functional.interpolate(x, size=lab.shape[1:])
+    cw = class_weights.to(device=x.device, dtype=dt)
+    num = torch.nn.functional.cross_entropy(x, lab, weight=cw, ignore_index=0, reduction="sum")
+    den = (cw[lab] * (lab > 0).to(dt)).sum()
+    return weight * (num / torch.where(den > 0, den, torch.ones_like(den)))
+
+
+def imgseg_loss(seg_logits, seg_labels, class_weights, weight=1.0):
+    """``imgseg=True``: weight * cross entropy of the segmentation head's logits [BN, K, h, w] against the projected LiDAR
+    labels [BN, H, W] (fp32 as the loader writes them, or int64).  fp32 CUDA logits with ``IMGSEG`` on and h <= H, w <= W run on
+    the fused HIP path (channels-last logits are made contiguous, int64 labels are converted: 154 kB and 2 MB at the model's
+    size), anything else (CPU, other dtypes, the switch off) on ``imgseg_loss_tensor``."""
+    _imgseg_check(seg_logits, seg_labels, class_weights)
+    h, w = seg_logits.shape[-2:]
+    H, W = seg_labels.shape[-2:]
+    if (IMGSEG and seg_logits.is_cuda and seg_labels.is_cuda and seg_logits.dtype == torch.float32 and h <= H and w <= W
+            and seg_logits.numel() > 0 and seg_labels.numel() > 0):
+        lab = seg_labels if seg_labels.dtype == torch.float32 else seg_labels.to(torch.float32)
+        cw = class_weights.to(device=seg_logits.device, dtype=torch.float32).contiguous()
+        return _ImgSegCe.apply(seg_logits.contiguous(), lab.contiguous(), cw, weight)
+    return imgseg_loss_tensor(seg_logits, seg_labels, class_weights, weight)
+
+
 OCC_TAIL = os.environ.get("SSBEV_OCC_TAIL", "1") != "0"      # scalar loss algebra in one launch (0 = ~110 tiny ATen ops)
 
 

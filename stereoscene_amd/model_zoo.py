@@ -15,7 +15,8 @@ def image_branch_cfg(arch="b7"):
 
 
 def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False, loss_depth_type="bce", voxel_ohem=0.0,
-              ohem_topk=0.25, frustum_dist=0.0, voxel_dice=0.0, voxel_lga=0.0):
+              ohem_topk=0.25, frustum_dist=0.0, voxel_dice=0.0, voxel_lga=0.0, imgseg=False, loss_seg_weight=1.0,
+              lift_with_imgseg=False, imgseg_labels="img_seg"):
     """Same structure and hyper-parameters as the reference config's ``model`` dict for the sizes in ``cfg`` (a
     synthetic.CFG_*).  ``image_branch=False`` (default, the benchmarked hot path a1-a16) leaves the 2-D
     image backbone/neck out: the detector then takes the image-neck features in place of raw images.  ``loss_depth_type``:
@@ -24,7 +25,14 @@ def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False, 
     ``frustum_dist`` > 0 switches the head's frustum-proportion loss on with that weight
     (``semkitti_loss_weight_cfg.frustum_dist``, ``use_frustum_loss=True``); the training call then needs ``frustums_ids`` / ``frustums_class_dists`` (pipelines.CreateRelationLabels).
     ``voxel_dice`` / ``voxel_lga`` > 0 switch the head's soft-Dice / LGA-weighted losses on with that weight
-    (``semkitti_loss_weight_cfg.voxel_dice`` / ``.voxel_lga``, ``use_dice_loss=True`` / ``use_lga_loss=True``)."""
+    (``semkitti_loss_weight_cfg.voxel_dice`` / ``.voxel_lga``, ``use_dice_loss=True`` / ``use_lga_loss=True``).
+    ``imgseg=True`` builds the view transformer's image-view segmentation head and adds ``loss_imgseg`` (weight
+    ``loss_seg_weight``); the training call then needs the label map named by ``imgseg_labels`` ("img_seg", the reference's
+    right-view map, or "img_seg_left").  ``lift_with_imgseg=True`` lifts the 20 class probabilities with the features: the 3-D
+    encoder then takes ``numC_Trans + 20`` channels."""
+    seg = dict(imgseg=True, imgseg_class=20, loss_seg_weight=float(loss_seg_weight), lift_with_imgseg=bool(lift_with_imgseg)) \
+        if imgseg else {}
+    bev_in = numC_Trans + (20 if imgseg and lift_with_imgseg else 0)
     norm_cfg = dict(type="GN", num_groups=32, requires_grad=True)
     channels = [128, 256, 512]
     return dict(
@@ -33,8 +41,8 @@ def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False, 
             type="ViewTransformerLiftSplatShootVoxel", downsample=cfg["downsample"], numC_input=640,
             cam_channels=30, semkitti=False, loss_depth_weight=1.0, grid_config=S.grid_config(cfg),
             data_config=dict(input_size=tuple(cfg["input_size"])), numC_Trans=numC_Trans, vp_megvii=False,
-            warp_align_corners=warp_align_corners, loss_depth_type=loss_depth_type),
-        img_bev_encoder_backbone=dict(type="CustomResNet3D", depth=18, num_stage=3, n_input_channels=numC_Trans,
+            warp_align_corners=warp_align_corners, loss_depth_type=loss_depth_type, **seg),
+        img_bev_encoder_backbone=dict(type="CustomResNet3D", depth=18, num_stage=3, n_input_channels=bev_in,
                                       block_inplanes=channels, out_indices=(0, 1, 2), norm_cfg=norm_cfg),
         img_bev_encoder_neck=dict(type="SECONDFPN3D", norm_cfg=norm_cfg, in_channels=channels,
                                   upsample_strides=[1, 2, 4], out_channels=[128, 128, 128]),
@@ -50,6 +58,7 @@ def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False, 
                                                      "frustum_dist": float(frustum_dist),
                                                      **({"voxel_dice": float(voxel_dice)} if voxel_dice > 0 else {}),
                                                      **({"voxel_lga": float(voxel_lga)} if voxel_lga > 0 else {})}),
+        **(dict(imgseg_labels=imgseg_labels) if imgseg else {}),
         train_cfg=dict(pts=None), test_cfg=dict(pts=None))
 
 

@@ -99,7 +99,11 @@ def lidar_depth_map(points, labels, rots, trans, intrins, post_rots, post_trans,
 class CreateDepthFromLiDAR:
     """Pipeline step of stereoscene.py:143.  Reads the frame's velodyne scan and lidarseg labels, and for the left then
     the right camera writes the sparse depth map into slot 7 of ``results['img_inputs'][k]``; ``points_occ``,
-    ``points_uv`` and ``img_seg`` are those of the right view (upstream overwrites them the same way)."""
+    ``points_uv`` and ``img_seg`` are those of the right view (upstream overwrites them the same way).
+
+    ``img_seg`` feeds the image-view segmentation loss (``imgseg=True``), whose head runs on the LEFT view's features: upstream
+    therefore supervises the left features with the right view's label map.  That stays the default; the left view's own map is
+    kept as ``img_seg_left`` and the detector's ``imgseg_labels="img_seg_left"`` selects it."""
 
     def __init__(self, point_cloud_range, grid_size, projective_filter=True, label_mapping="semantickitti.yaml",
                  lidar_root="./data/lidar/velodyne/dataset/sequences", lidarseg_root="./data/lidar/lidarseg/dataset/sequences",
@@ -141,6 +145,8 @@ class CreateDepthFromLiDAR:
         puv[:, :2] = (puv[:, :2] - 0.5) * 2
         results["points_uv"] = puv.unsqueeze(1)
         results["img_seg"] = img_seg
+        if k == 0:
+            results["img_seg_left"] = img_seg
         out = list(view)
         out[7] = depth.unsqueeze(0)
         return out
@@ -693,7 +699,8 @@ class CustomSemanticKITTILssDataset:
 def collate(samples, device="cuda"):
     """Batch of pipeline outputs -> the detector's call signature: ``img_inputs = (left10, right10)`` with a leading
     batch axis on every entry (what mmcv's collate + scatter produce upstream), ``gt_occ`` [B, X, Y, Z] int64; ``frustums_ids`` / ``frustums_class_dists`` / ``frustums_masks`` are stacked
-    when every sample carries them."""
+    when every sample carries them, and so are ``img_seg`` / ``img_seg_left`` ([B, H, W] float, the labels of the image-view
+    segmentation loss)."""
     on_gpu = torch.device(device).type == "cuda"
 
     def put(t):
@@ -722,6 +729,9 @@ def collate(samples, device="cuda"):
     for k in ("frustums_ids", "frustums_class_dists", "frustums_masks"):     # CreateRelationLabels' outputs, when every sample has them
         if all(k in s for s in samples):
             out[k] = put(torch.stack([torch.as_tensor(s[k]) for s in samples]))
+    for k in ("img_seg", "img_seg_left"):                                   # CreateDepthFromLiDAR's label maps
+        if all(k in s for s in samples):
+            out[k] = put(torch.stack([torch.as_tensor(s[k]).float() for s in samples]))
     return out
 
 

@@ -12,10 +12,19 @@ from ..registry import BACKBONES, DETECTORS, HEADS, NECKS
 
 @DETECTORS.register_module()
 class BEVDepthOccupancy(nn.Module):
+    """Extra kwarg ``imgseg_labels`` (used with ``img_view_transformer.imgseg=True``): the training kwarg the image-view
+    segmentation loss reads its labels from.  "img_seg" is the reference's choice (DET:243-246) -- the loader leaves the RIGHT
+    view's label map there (CreateDepthFromLiDAR overwrites it per view) although the head sees the LEFT view's features;
+    "img_seg_left" takes the left view's map, which ``pipelines.CreateDepthFromLiDAR`` stores next to it."""
+    IMGSEG_LABELS = ("img_seg", "img_seg_left")
+
     def __init__(self, img_backbone=None, img_neck=None, img_view_transformer=None, img_bev_encoder_backbone=None,
                  img_bev_encoder_neck=None, pts_bbox_head=None, loss_cfg=None, use_grid_mask=False,
-                 disable_loss_depth=False, train_cfg=None, test_cfg=None, **kwargs):
+                 disable_loss_depth=False, train_cfg=None, test_cfg=None, imgseg_labels="img_seg", **kwargs):
         super().__init__()
+        if imgseg_labels not in self.IMGSEG_LABELS:
+            raise ValueError(f"imgseg_labels must be one of {self.IMGSEG_LABELS}, got {imgseg_labels!r}")
+        self.imgseg_labels = imgseg_labels
         self.img_backbone = BACKBONES.build(img_backbone) if img_backbone and img_backbone["type"] in BACKBONES else None
         self.img_neck = NECKS.build(img_neck) if img_neck and img_neck["type"] in NECKS else None
         self.img_view_transformer = NECKS.build(img_view_transformer)
@@ -65,10 +74,17 @@ class BEVDepthOccupancy(nn.Module):
 
     def forward_train(self, points=None, img_metas=None, img_inputs=None, gt_occ=None, points_occ=None,
                       points_uv=None, **kwargs):
+        vt = getattr(self, "img_view_transformer", None)
+        with_seg = getattr(vt, "imgseg", False)
+        if with_seg and kwargs.get(self.imgseg_labels) is None:
+            raise KeyError(f"imgseg=True needs the training kwarg {self.imgseg_labels!r} (pipelines.CreateDepthFromLiDAR + "
+                           "collate provide it)")
         voxel_feats, img_feats, depth = self.extract_feat(points, img=img_inputs, img_metas=img_metas)
         losses = {}
         if not self.disable_loss_depth:
             losses["loss_depth"] = self.img_view_transformer.get_depth_loss(img_inputs[0][7], depth)   # DET:230
+        if with_seg:                                                                                   # DET:243-246
+            losses["loss_imgseg"] = vt.get_seg_loss(kwargs[self.imgseg_labels])
         losses.update(self.forward_pts_train(voxel_feats, gt_occ, points_occ, img_metas, **kwargs))
         return losses
 

@@ -513,8 +513,10 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
             raise ValueError(f"depth_kld_units must be one of {F.DEPTH_KLD_UNITS}, got {depth_kld_units!r}")
         self.depth_kld_units = depth_kld_units
         self.ablation = ablation
-        if imgseg or point_xyz_channel or use_voxel_net or vp_megvii:
+        if point_xyz_channel or use_voxel_net or vp_megvii:
             raise NotImplementedError("options unused by projects/configs/.../stereoscene.py are not built")
+        if imgseg and imgseg_class != 20:
+            raise ValueError(f"imgseg_class must be 20 (the SemanticKITTI class-weight table has 20 entries), got {imgseg_class}")
         self.grid_config, self.data_config = grid_config, data_config
         dx, bx, nx = gen_dx_bx(grid_config["xbound"], grid_config["ybound"], grid_config["zbound"])
         self.dx = nn.Parameter(dx, requires_grad=False)
@@ -525,12 +527,17 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
         self.D = self.frustum.shape[0]
         self.numC_input, self.numC_Trans, self.cam_channels = numC_input, numC_Trans, cam_channels
         self.loss_depth_weight, self.loss_depth_type = loss_depth_weight, loss_depth_type
-        self.imgseg, self.semkitti = False, semkitti
+        self.imgseg, self.semkitti = bool(imgseg), semkitti
         self.depth_net = DepthNet(numC_input, numC_input, numC_Trans, self.D, cam_channels=cam_channels)
         self.stereo_volume_net = GwcNet_volume_encoder(self.D, 32, warp_align_corners)
         self.volume_interaction = volume_interaction()
         self.cam_depth_range = grid_config["dbound"]
         self.constant_std = 0.5                       # VT:298: the only value the reference can run with (see get_klv_depth_loss)
+        self.forward_dic = {}
+        if self.imgseg:                               # auxiliary image-view segmentation (VT:327-340); nothing is built without it
+            self.imgseg_class, self.loss_seg_weight, self.lift_with_imgseg = imgseg_class, loss_seg_weight, bool(lift_with_imgseg)
+            self.img_seg_head = nn.Sequential(BasicBlock2d(numC_input, numC_input), BasicBlock2d(numC_input, numC_input),
+                                              Conv2d(numC_input, imgseg_class, 1))
 
     # geometry -------------------------------------------------------------------------------
     def create_frustum(self):
@@ -682,6 +689,22 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
         return F.depth_kld_loss(depth_labels, depth_preds, self.downsample, self.cam_depth_range, self.loss_depth_weight,
                                 self.constant_std, self.depth_kld_units)
 
+    def get_seg_loss(self, seg_labels):
+        """Image-view segmentation loss (VT:418-430), already multiplied by ``loss_seg_weight``: the head's logits of the last
+        ``forward`` (``forward_dic['imgseg_logits']``, [B*N, 20, fH, fW]) against the projected LiDAR labels [B*N, H, W] (float
+        or int64; 0 = no return = ignored), class-weighted with 1 / log(class frequency + 0.001).  The reference up-samples the
+        logits to the image (nearest) and runs CrossEntropyLoss(ignore_index=0); ``functional.imgseg_loss`` computes the same
+        number from a label histogram per feature pixel.  No labelled pixel gives 0 with a zero gradient (the reference: NaN);
+        labels outside [0, 20) are ignored (the reference raises)."""
+        if not self.imgseg:
+            raise RuntimeError("get_seg_loss needs imgseg=True")
+        if "imgseg_logits" not in self.forward_dic:
+            raise RuntimeError("get_seg_loss needs a forward pass first")
+        from .losses import semkitti_class_weights
+        logits = self.forward_dic["imgseg_logits"].float()                 # the reference's force_fp32
+        return F.imgseg_loss(logits, seg_labels.reshape(-1, *seg_labels.shape[-2:]), semkitti_class_weights(),
+                             self.loss_seg_weight)
+
     def get_depth_loss(self, depth_labels, depth_preds):
         """Depth loss (VT:375-416): ``loss_depth_type`` "bce" (below) or "kld" (get_klv_depth_loss)."""
         if self.loss_depth_type == "kld":
@@ -710,6 +733,8 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
         # geometry first: its tiny host-side 3x3 inverses must not stall the queued device work
         tables = self._cached_tables(rots, trans, intrins, post_rots, post_trans, bda)
         B, N, C, H, W = x.shape
+        if self.imgseg:                               # on the caller's stream, where x lives (VT:499-500)
+            self.forward_dic["imgseg_logits"] = self.img_seg_head(x.view(B * N, C, H, W))
         # The monocular branch (DepthNet: 2-D layers on the 48 x 160 map, kernels of a few hundred workgroups that cannot
         # fill 256 CUs) and the stereo branch (3-D stack on the cost volume: chip-filling kernels with idle tails) are
         # independent until the MIE block.  DepthNet runs on a second HIP stream; its backward follows on that stream by
@@ -737,5 +762,8 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
             depth_prob = self.volume_interaction(stereo, depth_prob)
         elif self.ablation == "stereo_only":
             depth_prob = stereo
+        if self.imgseg and self.lift_with_imgseg:     # VT:512-514: the class probabilities ride along with the lifted features
+            seg_prob = F.softmax(self.forward_dic["imgseg_logits"].float().contiguous(), dim=1)
+            img_feat = torch.cat((img_feat.float(), seg_prob), dim=1)
         bev_feat = F.lift_splat(depth_prob, img_feat, None, self.bx, self.dx, self.nx, grid_host=self._grid_host(), tables=tables)
         return bev_feat, depth_prob

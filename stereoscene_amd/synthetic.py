@@ -176,6 +176,38 @@ def depth_kld_case(name):
     return gt, (w / w.sum(dim=1, keepdim=True)).float(), ds, dbound, units
 
 
+# Cases of the image-view segmentation loss tests (tools/make_golden_imgseg.py records the reference on them): name -> (BN,
+# (h, w) of the logits, (H, W) of the label map, fraction of labelled pixels).  A: exact 16 x 16 blocks, sparse labels of classes
+# 1 .. 19, two samples, one cell cleared; B: ratios 7.4 and 14.43 (rectangles of unequal size, the min(.., n - 1) clamp, cells of
+# up to 8 x 15 = 120 pixels: two passes of a wavefront), every pixel labelled with 0 .. 19; C: A's first sample with nothing
+# labelled; D: logits in +-80, cell (0, 0) with a single labelled pixel, cell (0, 1) with none; E: the model's own sizes.
+IMGSEG_CASES = {"A": (2, (3, 5), (48, 80), 0.05), "B": (2, (5, 7), (37, 101), 1.0), "C": (1, (3, 5), (48, 80), 0.0),
+                "D": (1, (2, 3), (32, 48), 0.3), "E": (1, (24, 80), (384, 1280), 0.05)}
+IMGSEG_CLASSES = 20
+
+
+def imgseg_case(name):
+    """(seg_logits fp32 [BN,20,h,w], seg_labels fp32 [BN,H,W] with integer values 0 .. 19, 0 = unlabelled) of IMGSEG_CASES[name]."""
+    BN, (h, w), (H, W), density = IMGSEG_CASES[name]
+    K = IMGSEG_CLASSES
+    if name == "D":
+        logits = hash_uniform("imgseg_D/logits", (BN, K, h, w), -80.0, 80.0)
+    else:
+        logits = hash_normal(f"imgseg_{name}/logits", (BN, K, h, w), std=2.0)
+    if name == "B":                                   # every pixel carries a class, 0 among them
+        lab = hash_uniform("imgseg_B/cls", (BN, H, W), 0.0, float(K)).floor().clamp_(0, K - 1)
+    else:
+        cls = hash_uniform(f"imgseg_{name}/cls", (BN, H, W), 1.0, float(K)).floor().clamp_(1, K - 1)
+        u = hash_uniform(f"imgseg_{name}/mask", (BN, H, W), 0.0, 1.0)
+        lab = torch.where(u < density, cls, torch.zeros_like(cls))
+    if name == "A":
+        lab[1, 32:48, 64:80] = 0.0                    # cell (2, 4) of the second sample: no valid pixel
+    if name == "D":
+        lab[0, :16, :32] = 0.0
+        lab[0, 5, 9] = 7.0                            # cell (0, 0): one labelled pixel; cell (0, 1): none
+    return logits, lab
+
+
 _NORM_TOKENS = (".bn", ".gn", "norm")
 
 
@@ -380,7 +412,7 @@ def synthetic_sample(cfg, B=1, C_in=640, tag="s0", with_targets=True):
     """Image-neck outputs for both views + geometry + targets, all hash-generated.
 
     Returns a dict: x_l, x_r [B,1,C,fH,fW]; geo_l, geo_r (6-tuples); calib [B];
-    gt_depths [B,1,H,W]; gt_occ [B,X,Y,Z] int64 in {0..19, 255}.
+    gt_depths [B,1,H,W]; gt_occ [B,X,Y,Z] int64 in {0..19, 255}; img_seg [B,H,W] float in {0..19}, 0 = unlabelled.
     """
     H, W = cfg["input_size"]
     fH, fW = H // cfg["downsample"], W // cfg["downsample"]
@@ -399,4 +431,7 @@ def synthetic_sample(cfg, B=1, C_in=640, tag="s0", with_targets=True):
         c = (hash_uniform(f"{tag}/gt_occ", (B, X, Y, Z), 0.0, 20.0)).long().clamp_(0, 19)
         ig = hash_uniform(f"{tag}/gt_occ_ignore", (B, X, Y, Z), 0.0, 1.0) < 0.10
         out["gt_occ"] = torch.where(ig, torch.full_like(c, 255), c)
+        # image-view segmentation labels (CreateDepthFromLiDAR's img_seg): a class 1 .. 19 where the view has a LiDAR return
+        seg = hash_uniform(f"{tag}/img_seg", (B, H, W), 1.0, 20.0).floor().clamp_(1, 19)
+        out["img_seg"] = torch.where(u[:, 0] < 0.05, seg, torch.zeros_like(seg))
     return out
