@@ -36,6 +36,55 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// 64-lane inclusive scan (lane = position inside the wave).
+__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int t = __shfl_up(v, off, 64);
+    if (lane >= off) v += t;
+  }
+  return v;
+}
+
+// Fixed-order fold of n rows of NV doubles (row k at partial + k * stride) by one workgroup of 256 threads: thread t adds rows
+// t, t + 256, ... in that order, then a 128, 64, ..., 1 tree over LDS.  Every thread receives the NV totals.  The order is part
+// of the results' bits, which the fixtures of the loss kernels record: do not reshape it.
+template <int NV>
+__device__ __forceinline__ void block_fold256(const double* __restrict__ partial, long n, long stride, double (&out)[NV]) {
+  __shared__ double red[NV][256];
+  const int tid = threadIdx.x;
+  double a[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) a[j] = 0.0;
+  for (long k = tid; k < n; k += 256) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) a[j] += partial[(size_t)k * stride + j];
+  }
+#pragma unroll
+  for (int j = 0; j < NV; ++j) red[j][tid] = a[j];
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) red[j][tid] += red[j][tid + off];
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int j = 0; j < NV; ++j) out[j] = red[j][0];
+  __syncthreads();                               // (red is free again: a kernel may fold twice)
+}
 
 // ---- activation storage types (BASELINE configs[3]: bf16 activations between layers, fp32 arithmetic inside the kernels) ----
 // bf16 tensors cross the C ABI as raw 16-bit patterns; loads widen exactly, stores round to nearest even (v_cvt_pk_bf16_f32).

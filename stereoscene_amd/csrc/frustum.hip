@@ -49,15 +49,7 @@ struct FrCam {                               // kernel argument of the label pas
   int fs;
 };
 
-size_t fr_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
-bool fr_ok(const ssbev_frustum_dims* d) {
-  if (!d || d->B <= 0 || d->D <= 0 || d->H <= 0 || d->W <= 0 || d->C != NC) return false;
-  if (d->F < 1 || d->F > FR_MAXF) return false;
-  if (d->upsample != 0 && d->upsample != 1) return false;
-  const long long n = (long long)d->B * d->D * d->H * d->W * (d->upsample ? 8 : 1);
-  return n * NC < (1ll << 31);
-}
+bool fr_ok(const ssbev_frustum_dims* d) { return fine_dims_ok(d) && d->F >= 1 && d->F <= FR_MAXF; }
 
 FrPlan fr_plan(const ssbev_frustum_dims* d) {
   FrPlan p;
@@ -65,47 +57,18 @@ FrPlan fr_plan(const ssbev_frustum_dims* d) {
   p.N = (long long)d->B * p.Ns;
   p.nblk = (p.Ns + FR_TILE - 1) / FR_TILE;
   size_t o = 0;
-  p.part = o;  o += fr_align((size_t)d->B * p.nblk * d->F * NC * sizeof(double));
-  p.cum = o;   o += fr_align((size_t)d->F * NC * sizeof(double));
+  p.part = o;  o += ws_align256((size_t)d->B * p.nblk * d->F * NC * sizeof(double));
+  p.cum = o;   o += ws_align256((size_t)d->F * NC * sizeof(double));
   p.bytes = o;
   return p;
 }
 
-__device__ __forceinline__ float fr_wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ double fr_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// softmax of voxel v of sample b -> p[NC] (accurate expf).  UP: (D, H, W) is the coarse grid and v lives on [2D, 2H, 2W].
+// softmax of voxel v of sample b -> p[NC] (accurate expf; fine_logits: UP = the logits are on the coarse grid)
 template <bool UP>
 __device__ __forceinline__ void fr_softmax(const float* __restrict__ x, int b, int v, int Ns, int D, int H, int W, float* p) {
-  if (UP) {
-    int r = v;
-    const int ow = r % (2 * W); r /= 2 * W;
-    const int oh = r % (2 * H); r /= 2 * H;
-    upsampled_logits(x, b, D, H, W, r, oh, ow, p);
-  } else {
-    const float4* src = reinterpret_cast<const float4*>(x + ((size_t)b * Ns + v) * NC);
-#pragma unroll
-    for (int q = 0; q < NC / 4; ++q) {
-      const float4 t = src[q];
-      p[4 * q + 0] = t.x; p[4 * q + 1] = t.y; p[4 * q + 2] = t.z; p[4 * q + 3] = t.w;
-    }
-  }
-  float m = p[0];
-#pragma unroll
-  for (int c = 1; c < NC; ++c) m = p[c] > m ? p[c] : m;
-  float s = 0.0f;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) { p[c] = expf(p[c] - m); s += p[c]; }
-  const float inv = 1.0f / s;
+  fine_logits<UP>(x, b, v, Ns, D, H, W, p);
+  float m;
+  const float inv = 1.0f / exp_inplace(p, &m);
 #pragma unroll
   for (int c = 0; c < NC; ++c) p[c] *= inv;
 }
@@ -145,7 +108,7 @@ frustum_accum_kernel(const float* __restrict__ x, const uint8_t* __restrict__ id
         float acc = 0.0f;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-          const float s = fr_wave_sum(mine ? p[c] : 0.0f);
+          const float s = wave_sum(mine ? p[c] : 0.0f);
           acc = lane == c ? s : acc;
         }
         if (lane < NC) my[cur * NC + lane] += (double)acc;
@@ -207,7 +170,7 @@ frustum_final_kernel(const double* __restrict__ cum, const float* __restrict__ d
       }
   }
   const int n = __popcll(__ballot(counted));
-  const double sum = fr_wave_sum(term);
+  const double sum = wave_sum(term);
   if (f == 0) loss[0] = n ? (float)(sum / (double)n) : 0.0f;
   if (in) {
 #pragma unroll
@@ -228,11 +191,10 @@ frustum_bwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ ids,
   for (int i = threadIdx.x; i < F * NC; i += FR_T) gs[i] = grad_out[0] * g[i];
   __syncthreads();
   for (long i = (long)blockIdx.x * FR_T + threadIdx.x; i < N; i += (long)gridDim.x * FR_T) {
-    float4* dst = reinterpret_cast<float4*>(gdst + (size_t)i * NC);
+    float* dst = gdst + (size_t)i * NC;
     const int id = ids[i];
     if (id >= F) {
-#pragma unroll
-      for (int q = 0; q < NC / 4; ++q) dst[q] = make_float4(0, 0, 0, 0);
+      zero20(dst);
       continue;
     }
     float p[NC];
@@ -244,8 +206,7 @@ frustum_bwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ ids,
     float o[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) o[c] = p[c] * (row[c] - dot);
-#pragma unroll
-    for (int q = 0; q < NC / 4; ++q) dst[q] = make_float4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+    store20(dst, o);
   }
 }
 
@@ -285,11 +246,6 @@ frustum_labels_kernel(const uint8_t* __restrict__ labels, uint8_t* __restrict__ 
   }
 }
 
-unsigned fr_voxel_grid(long long n) {
-  const long long b = (n + FR_T - 1) / FR_T;
-  return (unsigned)(b < 4096 ? b : 4096);
-}
-
 }  // namespace
 
 extern "C" {
@@ -327,17 +283,14 @@ int ssbev_frustum_dist_bwd(const float* logits, const uint8_t* ids, const float*
   if (ws_bytes < ssbev_frustum_dist_bwd_workspace(d)) return SSBEV_EWORKSPACE;
   hipStream_t st = as_stream(stream);
   const FrPlan p = fr_plan(d);
-  if (!d->upsample) {
-    hipLaunchKernelGGL(frustum_bwd_kernel<false>, dim3(fr_voxel_grid(p.N)), dim3(FR_T), 0, st, logits, ids, g, grad_out,
-                       grad_logits, d->D, d->H, d->W, p.Ns, (long)p.N, d->F);
-    return ssbev_launch_status();
-  }
-  float* gfine = static_cast<float*>(ws);
-  hipLaunchKernelGGL(frustum_bwd_kernel<true>, dim3(fr_voxel_grid(p.N)), dim3(FR_T), 0, st, logits, ids, g, grad_out, gfine, d->D,
-                     d->H, d->W, p.Ns, (long)p.N, d->F);
-  ssbev_upsample_dims u = {d->B, d->D, d->H, d->W, NC};
-  const int rc = ssbev_trilinear2x_bwd(gfine, grad_logits, &u, stream);
-  return rc != SSBEV_OK ? rc : ssbev_launch_status();
+  float* gfine = d->upsample ? static_cast<float*>(ws) : grad_logits;
+  if (!d->upsample)
+    hipLaunchKernelGGL(frustum_bwd_kernel<false>, dim3(voxel_grid(p.N)), dim3(FR_T), 0, st, logits, ids, g, grad_out, gfine, d->D,
+                       d->H, d->W, p.Ns, (long)p.N, d->F);
+  else
+    hipLaunchKernelGGL(frustum_bwd_kernel<true>, dim3(voxel_grid(p.N)), dim3(FR_T), 0, st, logits, ids, g, grad_out, gfine, d->D,
+                       d->H, d->W, p.Ns, (long)p.N, d->F);
+  return finish_fine_grad(gfine, grad_logits, d->B, d->D, d->H, d->W, stream);
 }
 
 int ssbev_frustum_labels(const uint8_t* labels, uint8_t* ids, int32_t* counts, int X, int Y, int Z, const float* params,
@@ -359,7 +312,7 @@ int ssbev_frustum_labels(const uint8_t* labels, uint8_t* ids, int32_t* counts, i
   cam.fs = frustum_size;
   hipStream_t st = as_stream(stream);
   if (hipMemsetAsync(counts, 0, (size_t)frustum_size * frustum_size * NC * sizeof(int32_t), st) != hipSuccess) return SSBEV_ELAUNCH;
-  hipLaunchKernelGGL(frustum_labels_kernel, dim3(fr_voxel_grid(n)), dim3(FR_T), 0, st, labels, ids, counts, Y, Z, (long)n, cam);
+  hipLaunchKernelGGL(frustum_labels_kernel, dim3(voxel_grid(n)), dim3(FR_T), 0, st, labels, ids, counts, Y, Z, (long)n, cam);
   return ssbev_launch_status();
 }
 

@@ -35,11 +35,6 @@ __device__ int first_at_least(int c, float scale, int n_in, int n_out) {
   return i;
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
@@ -89,7 +84,7 @@ imgseg_ce_fwd_kernel(const float* __restrict__ logits, const float* __restrict__
   cell_softmax_terms(z, live, &m, &esum);
   const double nw = live ? (double)n * (double)cw[lane] : 0.0;
   const double nll = ((double)m - (double)z) + (double)logf(esum);                // lse - z_c
-  const double num = wave_sum_d(nw * nll), den = wave_sum_d(nw);
+  const double num = wave_sum(nw * nll), den = wave_sum(nw);
   if (live) counts[(size_t)cell * MAXK + lane] = n;
   if (lane == 0) { partial[(size_t)cell * 2] = num; partial[(size_t)cell * 2 + 1] = den; }
 }
@@ -98,21 +93,11 @@ imgseg_ce_fwd_kernel(const float* __restrict__ logits, const float* __restrict__
 __global__ void __launch_bounds__(256)
 imgseg_ce_reduce_kernel(const double* __restrict__ partial, long cells, float weight, double* __restrict__ numden,
                         float* __restrict__ loss) {
-  __shared__ double red[2][256];
-  double a = 0.0, b = 0.0;
-  for (long k = threadIdx.x; k < cells; k += 256) { a += partial[(size_t)k * 2]; b += partial[(size_t)k * 2 + 1]; }
-  red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (threadIdx.x < off) {
-      red[0][threadIdx.x] += red[0][threadIdx.x + off];
-      red[1][threadIdx.x] += red[1][threadIdx.x + off];
-    }
-    __syncthreads();
-  }
+  double nd[2];
+  block_fold256(partial, cells, 2, nd);
   if (threadIdx.x == 0) {
-    numden[0] = red[0][0]; numden[1] = red[1][0];
-    loss[0] = red[1][0] > 0.0 ? (float)((double)weight * (red[0][0] / red[1][0])) : 0.0f;
+    numden[0] = nd[0]; numden[1] = nd[1];
+    loss[0] = nd[1] > 0.0 ? (float)((double)weight * (nd[0] / nd[1])) : 0.0f;
   }
 }
 
@@ -133,7 +118,7 @@ imgseg_ce_bwd_kernel(const float* __restrict__ logits, const float* __restrict__
   float m, esum;
   const float e = cell_softmax_terms(z, live, &m, &esum);
   const double nw = live ? (double)counts[(size_t)cell * MAXK + lane] * (double)cw[lane] : 0.0;
-  const double den_cell = wave_sum_d(nw);
+  const double den_cell = wave_sum(nw);
   if (live) grad[at] = den_cell != 0.0 ? (float)(scale * (((double)e / (double)esum) * den_cell - nw)) : 0.0f;
 }
 

@@ -40,26 +40,17 @@ struct LvPlan {
   size_t totals, hist, tilefg, partial, closs, keys_a, keys_b, ids_a, ids_b, bytes;
 };
 
-size_t lv_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
-bool lv_ok(const ssbev_lovasz_dims* d) {
-  if (!d || d->B <= 0 || d->D <= 0 || d->H <= 0 || d->W <= 0 || d->C != NC) return false;
-  if (d->upsample != 0 && d->upsample != 1) return false;
-  const long long n = (long long)d->B * d->D * d->H * d->W * (d->upsample ? 8 : 1);
-  return n * NC < (1ll << 31);
-}
-
 LvPlan lv_plan(const ssbev_lovasz_dims* d) {
   LvPlan p;
   p.N = (long long)d->B * d->D * d->H * d->W * (d->upsample ? 8 : 1);
   p.nblk = (int)((p.N + LV_TILE - 1) / LV_TILE);
   size_t o = 0;
-  p.totals = o;  o += lv_align((size_t)LV_PASSES * NC * LV_ND * sizeof(int));
-  p.hist = o;    o += lv_align((size_t)NC * LV_ND * p.nblk * sizeof(int));
-  p.tilefg = o;  o += lv_align((size_t)NC * p.nblk * sizeof(int));
-  p.partial = o; o += lv_align((size_t)NC * p.nblk * sizeof(double));
-  p.closs = o;   o += lv_align((size_t)NC * sizeof(double));
-  const size_t seg = lv_align((size_t)NC * p.N * sizeof(unsigned));
+  p.totals = o;  o += ws_align256((size_t)LV_PASSES * NC * LV_ND * sizeof(int));
+  p.hist = o;    o += ws_align256((size_t)NC * LV_ND * p.nblk * sizeof(int));
+  p.tilefg = o;  o += ws_align256((size_t)NC * p.nblk * sizeof(int));
+  p.partial = o; o += ws_align256((size_t)NC * p.nblk * sizeof(double));
+  p.closs = o;   o += ws_align256((size_t)NC * sizeof(double));
+  const size_t seg = ws_align256((size_t)NC * p.N * sizeof(unsigned));
   p.keys_a = o;  o += seg;
   p.keys_b = o;  o += seg;
   p.ids_a = o;   o += seg;
@@ -80,21 +71,6 @@ __device__ __forceinline__ unsigned long long lv_match(int digit, bool valid) {
   return m;
 }
 
-__device__ __forceinline__ int lv_wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_up(v, off, 64);
-    if (lane >= off) v += t;
-  }
-  return v;
-}
-
-__device__ __forceinline__ double lv_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // live length of class c's segment: the first pass walks all N slots (ignored voxels hold LV_INVALID), later ones the M
 // compacted elements; an absent class has none
 template <bool FIRST>
@@ -104,24 +80,10 @@ __device__ __forceinline__ int lv_live(const int32_t* __restrict__ counts, int c
 }
 
 // ---------------------------------------------------------------- key pass
-// UP: (D, H, W) is the coarse grid and voxel i lives on [B, 2D, 2H, 2W]; otherwise the logits sit on the label grid.
+// softmax of flat voxel i -> z[NC] (fine_logits_flat: UP = the logits are on the coarse grid)
 template <bool UP>
 __device__ __forceinline__ void lv_probs(const float* __restrict__ x, long i, int D, int H, int W, float* z) {
-  if (UP) {
-    long r = i;
-    const int ow = (int)(r % (2 * W)); r /= 2 * W;
-    const int oh = (int)(r % (2 * H)); r /= 2 * H;
-    const int od = (int)(r % (2 * D));
-    const int b = (int)(r / (2 * D));
-    upsampled_logits(x, b, D, H, W, od, oh, ow, z);
-  } else {
-    const float4* src = reinterpret_cast<const float4*>(x + (size_t)i * NC);
-#pragma unroll
-    for (int q = 0; q < NC / 4; ++q) {
-      const float4 v = src[q];
-      z[4 * q + 0] = v.x; z[4 * q + 1] = v.y; z[4 * q + 2] = v.z; z[4 * q + 3] = v.w;
-    }
-  }
+  fine_logits_flat<UP>(x, i, D, H, W, z);
   int am;
   softmax_inplace(z, &am);
 }
@@ -199,7 +161,7 @@ lovasz_scan_kernel(int32_t* __restrict__ hist, const int32_t* __restrict__ total
   if (n == 0) return;
   const int live = (n + LV_TILE - 1) / LV_TILE;
   int part = tid < d ? totals[c * LV_ND + tid] : 0;
-  part = lv_wave_incl_scan(part, lane);
+  part = wave_incl_scan(part, lane);
   if (lane == 63) wsum[wave] = part;
   __syncthreads();
   if (tid == 0) carry_s = wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -208,7 +170,7 @@ lovasz_scan_kernel(int32_t* __restrict__ hist, const int32_t* __restrict__ total
   for (int c0 = 0; c0 < live; c0 += LV_T) {
     const int i = c0 + tid;
     const int v = i < live ? row[i] : 0;
-    const int incl = lv_wave_incl_scan(v, lane);
+    const int incl = wave_incl_scan(v, lane);
     if (lane == 63) wsum[wave] = incl;
     __syncthreads();
     int before = carry_s;
@@ -302,8 +264,7 @@ lovasz_tilefg_kernel(const unsigned* __restrict__ keys, const int32_t* __restric
     const long e = base + j * LV_T + tid;
     f += e < n ? (int)(seg[e] & 1u) : 0;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) f += __shfl_xor(f, off, 64);
+  f = wave_sum(f);
   if ((tid & 63) == 0) wsum[tid >> 6] = f;
   __syncthreads();
   if (tid == 0) tilefg[(size_t)c * nblk + blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -327,8 +288,7 @@ lovasz_dot_kernel(const unsigned* __restrict__ keys, const int32_t* __restrict__
   // foreground elements in front of this tile
   int before = 0;
   for (int b = tid; b < (int)blockIdx.x; b += LV_T) before += tilefg[(size_t)c * nblk + b];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off, 64);
+  before = wave_sum(before);
   if (lane == 0) wsum[wave] = before;
   __syncthreads();
   if (tid == 0) carry_s = wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -341,7 +301,7 @@ lovasz_dot_kernel(const unsigned* __restrict__ keys, const int32_t* __restrict__
     const bool valid = e < n;
     const unsigned k = valid ? kseg[e] : 0u;
     const int fg = (int)(k & 1u);
-    const int incl = lv_wave_incl_scan(fg, lane);
+    const int incl = wave_incl_scan(fg, lane);
     if (lane == 63) wsum[wave] = incl;
     __syncthreads();
     int f = carry_s + incl;
@@ -357,7 +317,7 @@ lovasz_dot_kernel(const unsigned* __restrict__ keys, const int32_t* __restrict__
     if (tid == 0) carry_s += wsum[0] + wsum[1] + wsum[2] + wsum[3];
     __syncthreads();
   }
-  acc = lv_wave_sum(acc);
+  acc = wave_sum(acc);
   if (lane == 0) dsum[wave] = acc;
   __syncthreads();
   if (tid == 0) partial[(size_t)c * nblk + blockIdx.x] = ((dsum[0] + dsum[1]) + dsum[2]) + dsum[3];
@@ -367,19 +327,12 @@ lovasz_dot_kernel(const unsigned* __restrict__ keys, const int32_t* __restrict__
 __global__ void __launch_bounds__(LV_T)
 lovasz_class_kernel(const double* __restrict__ partial, const int32_t* __restrict__ counts, int N, int nblk,
                     double* __restrict__ closs) {
-  __shared__ double red[LV_T];
-  const int c = blockIdx.x, tid = threadIdx.x;
+  const int c = blockIdx.x;
   const int n = lv_live<false>(counts, c, N);
   const int live = (n + LV_TILE - 1) / LV_TILE;
-  double a = 0.0;
-  for (int b = tid; b < live; b += LV_T) a += partial[(size_t)c * nblk + b];
-  red[tid] = a;
-  __syncthreads();
-  for (int off = LV_T / 2; off > 0; off >>= 1) {
-    if (tid < off) red[tid] += red[tid + off];
-    __syncthreads();
-  }
-  if (tid == 0) closs[c] = red[0];
+  double a[1];
+  block_fold256(partial + (size_t)c * nblk, live, 1, a);
+  if (threadIdx.x == 0) closs[c] = a[0];
 }
 
 // loss = mean of closs over the present classes (0 when none); counts[NC + 1] = n_present
@@ -410,20 +363,14 @@ lovasz_bwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ label
   __syncthreads();
   for (long i = (long)blockIdx.x * LV_T + threadIdx.x; i < N; i += (long)gridDim.x * LV_T) {
     const int t = label[i];
-    float4* dst = reinterpret_cast<float4*>(gdst + (size_t)i * NC);
+    float* dst = gdst + (size_t)i * NC;
     if (t == ignore) {
-#pragma unroll
-      for (int q = 0; q < NC / 4; ++q) dst[q] = make_float4(0, 0, 0, 0);
+      zero20(dst);
       continue;
     }
     float p[NC], g[NC];
     lv_probs<UP>(x, i, D, H, W, p);
-    const float4* dsrc = reinterpret_cast<const float4*>(dj + (size_t)i * NC);
-#pragma unroll
-    for (int q = 0; q < NC / 4; ++q) {
-      const float4 v = dsrc[q];
-      g[4 * q + 0] = v.x; g[4 * q + 1] = v.y; g[4 * q + 2] = v.z; g[4 * q + 3] = v.w;
-    }
+    load20(dj + (size_t)i * NC, g);
     float dot = 0.0f;
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
@@ -432,16 +379,12 @@ lovasz_bwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ label
       g[c] = present[c] ? s * g[c] * scale[c] : 0.0f;      // (dj of an absent class was never written: select, not multiply)
       dot += g[c] * p[c];
     }
+    float4* d4 = reinterpret_cast<float4*>(dst);
 #pragma unroll
     for (int q = 0; q < NC / 4; ++q)
-      dst[q] = make_float4(p[4 * q] * (g[4 * q] - dot), p[4 * q + 1] * (g[4 * q + 1] - dot),
+      d4[q] = make_float4(p[4 * q] * (g[4 * q] - dot), p[4 * q + 1] * (g[4 * q + 1] - dot),
                            p[4 * q + 2] * (g[4 * q + 2] - dot), p[4 * q + 3] * (g[4 * q + 3] - dot));
   }
-}
-
-unsigned lv_voxel_grid(long long N) {
-  const long long b = (N + LV_T - 1) / LV_T;
-  return (unsigned)(b < 4096 ? b : 4096);
 }
 
 template <bool FIRST>
@@ -461,11 +404,11 @@ extern "C" {
 
 int ssbev_lovasz_num_counts(void) { return LV_NCNT; }
 
-size_t ssbev_lovasz_workspace(const ssbev_lovasz_dims* d) { return lv_ok(d) ? lv_plan(d).bytes : 0; }
+size_t ssbev_lovasz_workspace(const ssbev_lovasz_dims* d) { return fine_dims_ok(d) ? lv_plan(d).bytes : 0; }
 
 int ssbev_lovasz_fwd(const float* logits, const uint8_t* label, float* loss, float* dj, int32_t* counts,
                      const ssbev_lovasz_dims* d, void* ws, size_t ws_bytes, ssbev_stream_t stream) {
-  if (!lv_ok(d) || !logits || !label || !loss || !dj || !counts || !ws) return SSBEV_EINVAL;
+  if (!fine_dims_ok(d) || !logits || !label || !loss || !dj || !counts || !ws) return SSBEV_EINVAL;
   const LvPlan p = lv_plan(d);
   if (ws_bytes < p.bytes) return SSBEV_EWORKSPACE;
   hipStream_t st = as_stream(stream);
@@ -483,10 +426,10 @@ int ssbev_lovasz_fwd(const float* logits, const uint8_t* label, float* loss, flo
   if (hipMemsetAsync(totals, 0, (size_t)LV_PASSES * NC * LV_ND * sizeof(int32_t), st) != hipSuccess) return SSBEV_ELAUNCH;
   const int N = (int)p.N;
   if (d->upsample)
-    hipLaunchKernelGGL(lovasz_key_kernel<true>, dim3(lv_voxel_grid(p.N)), dim3(LV_T), 0, st, logits, label, ka, counts, d->D,
+    hipLaunchKernelGGL(lovasz_key_kernel<true>, dim3(voxel_grid(p.N)), dim3(LV_T), 0, st, logits, label, ka, counts, d->D,
                        d->H, d->W, (long)p.N, d->ignore);
   else
-    hipLaunchKernelGGL(lovasz_key_kernel<false>, dim3(lv_voxel_grid(p.N)), dim3(LV_T), 0, st, logits, label, ka, counts, d->D,
+    hipLaunchKernelGGL(lovasz_key_kernel<false>, dim3(voxel_grid(p.N)), dim3(LV_T), 0, st, logits, label, ka, counts, d->D,
                        d->H, d->W, (long)p.N, d->ignore);
   lv_sort_pass<true>(ka, nullptr, kb, ib, counts, p, 0, hist, totals, st);
   lv_sort_pass<false>(kb, ib, ka, ia, counts, p, 1, hist, totals, st);
@@ -500,29 +443,26 @@ int ssbev_lovasz_fwd(const float* logits, const uint8_t* label, float* loss, flo
 }
 
 size_t ssbev_lovasz_bwd_workspace(const ssbev_lovasz_dims* d) {
-  if (!lv_ok(d)) return 0;
+  if (!fine_dims_ok(d)) return 0;
   return d->upsample ? (size_t)lv_plan(d).N * NC * sizeof(float) : 0;
 }
 
 int ssbev_lovasz_bwd(const float* logits, const uint8_t* label, const float* dj, const int32_t* counts,
                      const float* grad_out, float* grad_logits, const ssbev_lovasz_dims* d, void* ws, size_t ws_bytes,
                      ssbev_stream_t stream) {
-  if (!lv_ok(d) || !logits || !label || !dj || !counts || !grad_out || !grad_logits) return SSBEV_EINVAL;
+  if (!fine_dims_ok(d) || !logits || !label || !dj || !counts || !grad_out || !grad_logits) return SSBEV_EINVAL;
   if (d->upsample && !ws) return SSBEV_EINVAL;
   if (ws_bytes < ssbev_lovasz_bwd_workspace(d)) return SSBEV_EWORKSPACE;
   hipStream_t st = as_stream(stream);
   const LvPlan p = lv_plan(d);
-  if (!d->upsample) {
-    hipLaunchKernelGGL(lovasz_bwd_kernel<false>, dim3(lv_voxel_grid(p.N)), dim3(LV_T), 0, st, logits, label, dj, counts,
-                       grad_out, grad_logits, d->D, d->H, d->W, (long)p.N, d->ignore);
-    return ssbev_launch_status();
-  }
-  float* gfine = static_cast<float*>(ws);
-  hipLaunchKernelGGL(lovasz_bwd_kernel<true>, dim3(lv_voxel_grid(p.N)), dim3(LV_T), 0, st, logits, label, dj, counts, grad_out,
-                     gfine, d->D, d->H, d->W, (long)p.N, d->ignore);
-  ssbev_upsample_dims u = {d->B, d->D, d->H, d->W, NC};
-  const int rc = ssbev_trilinear2x_bwd(gfine, grad_logits, &u, stream);
-  return rc != SSBEV_OK ? rc : ssbev_launch_status();
+  float* gfine = d->upsample ? static_cast<float*>(ws) : grad_logits;
+  if (!d->upsample)
+    hipLaunchKernelGGL(lovasz_bwd_kernel<false>, dim3(voxel_grid(p.N)), dim3(LV_T), 0, st, logits, label, dj, counts, grad_out,
+                       gfine, d->D, d->H, d->W, (long)p.N, d->ignore);
+  else
+    hipLaunchKernelGGL(lovasz_bwd_kernel<true>, dim3(voxel_grid(p.N)), dim3(LV_T), 0, st, logits, label, dj, counts, grad_out,
+                       gfine, d->D, d->H, d->W, (long)p.N, d->ignore);
+  return finish_fine_grad(gfine, grad_logits, d->B, d->D, d->H, d->W, stream);
 }
 
 }  // extern "C"

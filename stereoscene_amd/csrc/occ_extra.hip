@@ -10,7 +10,7 @@
 //               a 20-way softmax in registers, per-wave float sums folded in wave order into per-workgroup double partials and a
 //               fixed-order fold.  No float atomics, nothing read back, the up-sampled volume is never written.
 #include "common.h"
-#include "occ_fine.h"     // NC, upsampled_logits, softmax_inplace
+#include "occ_fine.h"     // NC, fine_logits_flat, softmax_inplace, the host helpers
 
 namespace {
 
@@ -70,13 +70,8 @@ occ_lga_fwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ labe
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int t = label[i];
     if (t >= NC) continue;                       // 255 = ignore
-    long r = i;
-    const int ow = (int)(r % (2 * W)); r /= 2 * W;
-    const int oh = (int)(r % (2 * H)); r /= 2 * H;
-    const int od = (int)(r % (2 * D));
-    const int b = (int)(r / (2 * D));
     float z[NC];
-    upsampled_logits(x, b, D, H, W, od, oh, ow, z);
+    fine_logits_flat<true>(x, i, D, H, W, z);
     float zt_raw = 0.0f;
 #pragma unroll
     for (int c = 0; c < NC; ++c) zt_raw = (c == t) ? z[c] : zt_raw;
@@ -99,21 +94,11 @@ occ_lga_fwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ labe
 // numden = sums over the blocks in a fixed order; loss = num / den, 0 when nothing is labelled
 __global__ void __launch_bounds__(256)
 occ_lga_reduce_kernel(const double* __restrict__ partial, int nblocks, double* __restrict__ numden, float* __restrict__ loss) {
-  __shared__ double red[2][256];
-  double a = 0.0, b = 0.0;
-  for (int k = threadIdx.x; k < nblocks; k += 256) { a += partial[(size_t)k * 2]; b += partial[(size_t)k * 2 + 1]; }
-  red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (threadIdx.x < off) {
-      red[0][threadIdx.x] += red[0][threadIdx.x + off];
-      red[1][threadIdx.x] += red[1][threadIdx.x + off];
-    }
-    __syncthreads();
-  }
+  double nd[2];
+  block_fold256(partial, nblocks, 2, nd);
   if (threadIdx.x == 0) {
-    numden[0] = red[0][0]; numden[1] = red[1][0];
-    loss[0] = red[1][0] > 0.0 ? (float)(red[0][0] / red[1][0]) : 0.0f;
+    numden[0] = nd[0]; numden[1] = nd[1];
+    loss[0] = nd[1] > 0.0 ? (float)(nd[0] / nd[1]) : 0.0f;
   }
 }
 
@@ -128,27 +113,20 @@ occ_lga_bwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ labe
   const long total = (long)B * 8 * D * H * W;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int t = label[i];
-    float4* dst = reinterpret_cast<float4*>(gfine + (size_t)i * NC);
+    float* dst = gfine + (size_t)i * NC;
     if (t >= NC || scale == 0.0f) {
-#pragma unroll
-      for (int q = 0; q < NC / 4; ++q) dst[q] = make_float4(0, 0, 0, 0);
+      zero20(dst);
       continue;
     }
-    long r = i;
-    const int ow = (int)(r % (2 * W)); r /= 2 * W;
-    const int oh = (int)(r % (2 * H)); r /= 2 * H;
-    const int od = (int)(r % (2 * D));
-    const int b = (int)(r / (2 * D));
     float z[NC];
-    upsampled_logits(x, b, D, H, W, od, oh, ow, z);
+    fine_logits_flat<true>(x, i, D, H, W, z);
     int am;
     softmax_inplace(z, &am);
     const float k = scale * cw[t] * (alpha + beta * (0.5f * (float)lga2[i]));
     float g[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) g[c] = k * (z[c] - (c == t ? 1.0f : 0.0f));
-#pragma unroll
-    for (int q = 0; q < NC / 4; ++q) dst[q] = make_float4(g[4 * q], g[4 * q + 1], g[4 * q + 2], g[4 * q + 3]);
+    store20(dst, g);
   }
 }
 
@@ -211,9 +189,7 @@ int ssbev_occ_lga_bwd(const float* logits, const uint8_t* label, const uint8_t* 
   float* gfine = static_cast<float*>(ws);
   hipLaunchKernelGGL(occ_lga_bwd_kernel, dim3((unsigned)min((long)cdiv(fine, 256), 4096L)), dim3(256), 0, as_stream(stream),
                      logits, label, lga2, class_weight, alpha, beta, numden, grad_out, gfine, d->B, d->D, d->H, d->W);
-  ssbev_upsample_dims u = {d->B, d->D, d->H, d->W, NC};
-  const int rc = ssbev_trilinear2x_bwd(gfine, grad_logits, &u, stream);
-  return rc != SSBEV_OK ? rc : ssbev_launch_status();
+  return finish_fine_grad(gfine, grad_logits, d->B, d->D, d->H, d->W, stream);
 }
 
 }  // extern "C"

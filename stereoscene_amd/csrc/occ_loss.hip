@@ -14,7 +14,7 @@
 // written once at the fine resolution (a scratch buffer of the backward pass only) and pulled back to the coarse
 // grid by the gather-form x2 kernel of trilinear.hip: no atomics, deterministic.
 #include "common.h"
-#include "occ_fine.h"     // NC, upsampled_logits, softmax_inplace (shared with lovasz.hip)
+#include "occ_fine.h"     // NC, fine_logits_flat, softmax_inplace, the host helpers
 
 namespace {
 
@@ -36,13 +36,8 @@ occ_loss_fwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ lab
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int t = label[i];
     if (t >= NC) continue;                       // 255 = ignore
-    long r = i;
-    const int ow = (int)(r % (2 * W)); r /= 2 * W;
-    const int oh = (int)(r % (2 * H)); r /= 2 * H;
-    const int od = (int)(r % (2 * D));
-    const int b = (int)(r / (2 * D));
     float z[NC];
-    upsampled_logits(x, b, D, H, W, od, oh, ow, z);
+    fine_logits_flat<true>(x, i, D, H, W, z);
     float zt_raw = 0.0f;
 #pragma unroll
     for (int c = 0; c < NC; ++c) zt_raw = (c == t) ? z[c] : zt_raw;
@@ -76,16 +71,9 @@ occ_loss_fwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ lab
 // sums[i] = sum over blocks in block order (deterministic given the per-block values)
 __global__ void occ_loss_reduce_kernel(const double* __restrict__ partial, int nblocks, double* __restrict__ sums) {
   const int i = blockIdx.x;
-  __shared__ double red[256];
-  double a = 0.0;
-  for (int b = threadIdx.x; b < nblocks; b += 256) a += partial[(size_t)b * NS + i];
-  red[threadIdx.x] = a;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) sums[i] = red[0];
+  double a[1];
+  block_fold256(partial + i, nblocks, NS, a);
+  if (threadIdx.x == 0) sums[i] = a[0];
 }
 
 // coef = [a_ce, A[NC], Bc[NC]] (dL/dce_num, dL/dsum_p[c], dL/dnom[c]).  One thread per FINE voxel writes its
@@ -100,19 +88,13 @@ occ_loss_bwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ lab
   const long total = (long)B * 8 * D * H * W;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int t = label[i];
-    float4* dst = reinterpret_cast<float4*>(gfine + (size_t)i * NC);
+    float* dst = gfine + (size_t)i * NC;
     if (t >= NC) {
-#pragma unroll
-      for (int q = 0; q < NC / 4; ++q) dst[q] = make_float4(0, 0, 0, 0);
+      zero20(dst);
       continue;
     }
-    long r = i;
-    const int ow = (int)(r % (2 * W)); r /= 2 * W;
-    const int oh = (int)(r % (2 * H)); r /= 2 * H;
-    const int od = (int)(r % (2 * D));
-    const int b = (int)(r / (2 * D));
     float z[NC];
-    upsampled_logits(x, b, D, H, W, od, oh, ow, z);
+    fine_logits_flat<true>(x, i, D, H, W, z);
     int am;
     softmax_inplace(z, &am);
     float dot = 0.0f, wt = 0.0f;
@@ -128,8 +110,7 @@ occ_loss_bwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ lab
       const float Cc = cf[1 + c] + (c == t ? cf[1 + NC + c] : 0.0f);
       g[c] = wce * (z[c] - (c == t ? 1.0f : 0.0f)) + z[c] * (Cc - dot);
     }
-#pragma unroll
-    for (int q = 0; q < NC / 4; ++q) dst[q] = make_float4(g[4 * q], g[4 * q + 1], g[4 * q + 2], g[4 * q + 3]);
+    store20(dst, g);
   }
 }
 
@@ -146,11 +127,6 @@ __device__ __forceinline__ double nll1(double v, double& dv) {       // value an
   if (l > -100.0) { dv = -1.0 / v; return -l; }
   dv = 0.0;                                     // clamped (or NaN: torch.clamp passes it on with a zero gradient)
   return l != l ? l : 100.0;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 __global__ void __launch_bounds__(64)
@@ -272,9 +248,7 @@ int ssbev_occ_loss_bwd(const float* logits, const uint8_t* label, const float* c
   float* gfine = static_cast<float*>(ws);
   hipLaunchKernelGGL(occ_loss_bwd_kernel, dim3(4096), dim3(256), 0, as_stream(stream), logits, label, class_weight, coef,
                      gfine, d->B, d->D, d->H, d->W);
-  ssbev_upsample_dims u = {d->B, d->D, d->H, d->W, NC};
-  const int rc = ssbev_trilinear2x_bwd(gfine, grad_logits, &u, stream);
-  return rc != SSBEV_OK ? rc : ssbev_launch_status();
+  return finish_fine_grad(gfine, grad_logits, d->B, d->D, d->H, d->W, stream);
 }
 
 }  // extern "C"

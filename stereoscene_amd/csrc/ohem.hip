@@ -49,14 +49,8 @@ struct OhPlan {
   size_t lbits, hist, state, tiecnt, part_s, part_w, zero_from, zero_bytes, bytes;
 };
 
-size_t oh_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 bool oh_ok(const ssbev_ohem_dims* d) {
-  if (!d || d->B <= 0 || d->D <= 0 || d->H <= 0 || d->W <= 0 || d->C != NC) return false;
-  if (d->upsample != 0 && d->upsample != 1) return false;
-  if (!(d->top_k > 0.0 && d->top_k <= 1.0)) return false;        // (a NaN fails both)
-  const long long n = (long long)d->B * d->D * d->H * d->W * (d->upsample ? 8 : 1);
-  return n * NC < (1ll << 31);
+  return fine_dims_ok(d) && d->top_k > 0.0 && d->top_k <= 1.0;     // (a NaN fails both)
 }
 
 OhPlan oh_plan(const ssbev_ohem_dims* d) {
@@ -65,61 +59,16 @@ OhPlan oh_plan(const ssbev_ohem_dims* d) {
   p.N = (long long)d->B * p.Ns;
   p.nblk = (p.Ns + OH_TILE - 1) / OH_TILE;
   size_t o = 0;
-  p.lbits = o;   o += oh_align((size_t)p.N * sizeof(unsigned));   // first: the per-voxel losses stay readable after the call
+  p.lbits = o;   o += ws_align256((size_t)p.N * sizeof(unsigned));   // first: the per-voxel losses stay readable after the call
   p.zero_from = o;
-  p.hist = o;    o += oh_align((size_t)d->B * OH_PASSES * OH_ND * sizeof(int));
-  p.state = o;   o += oh_align((size_t)d->B * sizeof(OhState));
+  p.hist = o;    o += ws_align256((size_t)d->B * OH_PASSES * OH_ND * sizeof(int));
+  p.state = o;   o += ws_align256((size_t)d->B * sizeof(OhState));
   p.zero_bytes = o - p.zero_from;
-  p.tiecnt = o;  o += oh_align((size_t)d->B * p.nblk * sizeof(int));
-  p.part_s = o;  o += oh_align((size_t)d->B * p.nblk * sizeof(double));
-  p.part_w = o;  o += oh_align((size_t)d->B * p.nblk * sizeof(double));
+  p.tiecnt = o;  o += ws_align256((size_t)d->B * p.nblk * sizeof(int));
+  p.part_s = o;  o += ws_align256((size_t)d->B * p.nblk * sizeof(double));
+  p.part_w = o;  o += ws_align256((size_t)d->B * p.nblk * sizeof(double));
   p.bytes = o;
   return p;
-}
-
-__device__ __forceinline__ int oh_wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_up(v, off, 64);
-    if (lane >= off) v += t;
-  }
-  return v;
-}
-
-__device__ __forceinline__ double oh_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// logits of voxel v of sample b -> z[NC].  UP: (D, H, W) is the coarse grid and v lives on [2D, 2H, 2W].
-template <bool UP>
-__device__ __forceinline__ void oh_logits(const float* __restrict__ x, int b, int v, int Ns, int D, int H, int W, float* z) {
-  if (UP) {
-    int r = v;
-    const int ow = r % (2 * W); r /= 2 * W;
-    const int oh = r % (2 * H); r /= 2 * H;
-    upsampled_logits(x, b, D, H, W, r, oh, ow, z);
-  } else {
-    const float4* src = reinterpret_cast<const float4*>(x + ((size_t)b * Ns + v) * NC);
-#pragma unroll
-    for (int q = 0; q < NC / 4; ++q) {
-      const float4 t = src[q];
-      z[4 * q + 0] = t.x; z[4 * q + 1] = t.y; z[4 * q + 2] = t.z; z[4 * q + 3] = t.w;
-    }
-  }
-}
-
-// z -> exp(z - max) in place; returns the sum, *mx the maximum (accurate expf)
-__device__ __forceinline__ float oh_exp_inplace(float* z, float* mx) {
-  float m = z[0];
-#pragma unroll
-  for (int c = 1; c < NC; ++c) m = z[c] > m ? z[c] : m;
-  float s = 0.0f;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) { z[c] = expf(z[c] - m); s += z[c]; }
-  *mx = m;
-  return s;
 }
 
 __device__ __forceinline__ bool oh_labelled(int t, int ignore) { return t != ignore && t < NC; }
@@ -147,12 +96,12 @@ ohem_loss_kernel(const float* __restrict__ x, const uint8_t* __restrict__ label,
       continue;
     }
     float z[NC];
-    oh_logits<UP>(x, b, v, Ns, D, H, W, z);
+    fine_logits<UP>(x, b, v, Ns, D, H, W, z);
     float zt = 0.0f;
 #pragma unroll
     for (int c = 0; c < NC; ++c) zt = (c == t) ? z[c] : zt;
     float m;
-    const float s = oh_exp_inplace(z, &m);
+    const float s = exp_inplace(z, &m);
     const float l = w[t] * (logf(s) - (zt - m));
     unsigned bits = __float_as_uint(l);
     if (l != l) bits = OH_QNAN;
@@ -201,7 +150,7 @@ ohem_pick_kernel(const int32_t* __restrict__ hist, OhState* __restrict__ state, 
   const unsigned prefix = pass == 0 ? 0u : state[b].prefix;
   const long long k = pass == 0 ? (long long)((double)state[b].M * top_k) : state[b].k;
   const int h = hist[((size_t)b * OH_PASSES + pass) * OH_ND + d];
-  int incl = oh_wave_incl_scan(h, lane);
+  int incl = wave_incl_scan(h, lane);
   if (lane == 63) wsum[wave] = incl;
   __syncthreads();                               // (also: every thread has read the state before one of them writes it)
   for (int w = 0; w < wave; ++w) incl += wsum[w];
@@ -233,8 +182,7 @@ ohem_tie_kernel(const unsigned* __restrict__ lbits, const OhState* __restrict__ 
     const unsigned k = e < Ns ? seg[e] : OH_MARK;
     n += (k != OH_MARK && k == T) ? 1 : 0;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+  n = wave_sum(n);
   if ((tid & 63) == 0) wsum[tid >> 6] = n;
   __syncthreads();
   if (tid == 0) tiecnt[(size_t)b * nblk + blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -256,8 +204,7 @@ ohem_select_kernel(const unsigned* __restrict__ lbits, const uint8_t* __restrict
   // ties in the tiles in front of this one
   int before = 0;
   for (int t = tid; t < (int)blockIdx.x; t += OH_T) before += tiecnt[(size_t)b * nblk + t];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off, 64);
+  before = wave_sum(before);
   if (lane == 0) wsum[wave] = before;
   const int base = blockIdx.x * OH_TILE;
   const size_t seg = (size_t)b * Ns;
@@ -274,7 +221,7 @@ ohem_select_kernel(const unsigned* __restrict__ lbits, const uint8_t* __restrict
   before = wsum[0] + wsum[1] + wsum[2] + wsum[3];
   if (wave == 0) {                               // voxel order inside the tile is (row j, wave, lane): 32 counts, one wave
     const int v = lane < OH_ITEMS * OH_WAVES ? rowcnt[lane] : 0;
-    const int incl = oh_wave_incl_scan(v, lane);
+    const int incl = wave_incl_scan(v, lane);
     if (lane < OH_ITEMS * OH_WAVES) rowcnt[lane] = incl - v;
   }
   __syncthreads();
@@ -296,8 +243,8 @@ ohem_select_kernel(const unsigned* __restrict__ lbits, const uint8_t* __restrict
       aw += (double)w[label[seg + e]];           // selected => labelled => label < NC
     }
   }
-  as = oh_wave_sum(as);
-  aw = oh_wave_sum(aw);
+  as = wave_sum(as);
+  aw = wave_sum(aw);
   if (lane == 0) { ds[wave] = as; dw[wave] = aw; }
   __syncthreads();
   if (tid == 0) {
@@ -310,20 +257,12 @@ ohem_select_kernel(const unsigned* __restrict__ lbits, const uint8_t* __restrict
 __global__ void __launch_bounds__(OH_T)
 ohem_final_kernel(const double* __restrict__ part_s, const double* __restrict__ part_w, int n, float* __restrict__ loss,
                   float* __restrict__ inv) {
-  __shared__ double rs[OH_T], rw[OH_T];
-  const int tid = threadIdx.x;
-  double s = 0.0, w = 0.0;
-  for (int i = tid; i < n; i += OH_T) { s += part_s[i]; w += part_w[i]; }
-  rs[tid] = s;
-  rw[tid] = w;
-  __syncthreads();
-  for (int off = OH_T / 2; off > 0; off >>= 1) {
-    if (tid < off) { rs[tid] += rs[tid + off]; rw[tid] += rw[tid + off]; }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    const double den = rw[0] > 1e-4 ? rw[0] : 1e-4;
-    loss[0] = (float)(rs[0] / den);
+  double s[1], w[1];
+  block_fold256(part_s, n, 1, s);
+  block_fold256(part_w, n, 1, w);
+  if (threadIdx.x == 0) {
+    const double den = w[0] > 1e-4 ? w[0] : 1e-4;
+    loss[0] = (float)(s[0] / den);
     inv[0] = (float)(1.0 / den);
   }
 }
@@ -338,29 +277,22 @@ ohem_bwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ label, 
   if (threadIdx.x < NC) w[threadIdx.x] = grad_out[0] * inv[0] * cw[threadIdx.x];
   __syncthreads();
   for (long i = (long)blockIdx.x * OH_T + threadIdx.x; i < N; i += (long)gridDim.x * OH_T) {
-    float4* dst = reinterpret_cast<float4*>(gdst + (size_t)i * NC);
+    float* dst = gdst + (size_t)i * NC;
     if (!mask[i]) {
-#pragma unroll
-      for (int q = 0; q < NC / 4; ++q) dst[q] = make_float4(0, 0, 0, 0);
+      zero20(dst);
       continue;
     }
     const int t = label[i];
     float p[NC];
-    oh_logits<UP>(x, (int)(i / Ns), (int)(i % Ns), Ns, D, H, W, p);
+    fine_logits<UP>(x, (int)(i / Ns), (int)(i % Ns), Ns, D, H, W, p);
     float m;
-    const float s = oh_exp_inplace(p, &m);
+    const float s = exp_inplace(p, &m);
     const float g = w[t] / s;
     float o[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) o[c] = g * p[c] - (c == t ? w[t] : 0.0f);
-#pragma unroll
-    for (int q = 0; q < NC / 4; ++q) dst[q] = make_float4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+    store20(dst, o);
   }
-}
-
-unsigned oh_voxel_grid(long long n) {
-  const long long b = (n + OH_T - 1) / OH_T;
-  return (unsigned)(b < 4096 ? b : 4096);
 }
 
 }  // namespace
@@ -383,7 +315,7 @@ int ssbev_ohem_ce_fwd(const float* logits, const uint8_t* label, const float* cl
   double* part_s = reinterpret_cast<double*>(w + p.part_s);
   double* part_w = reinterpret_cast<double*>(w + p.part_w);
   if (hipMemsetAsync(w + p.zero_from, 0, p.zero_bytes, st) != hipSuccess) return SSBEV_ELAUNCH;
-  const dim3 lgrid(oh_voxel_grid(p.Ns), d->B), tgrid(p.nblk, d->B);
+  const dim3 lgrid(voxel_grid(p.Ns), d->B), tgrid(p.nblk, d->B);
   if (d->upsample)
     hipLaunchKernelGGL(ohem_loss_kernel<true>, lgrid, dim3(OH_T), 0, st, logits, label, class_weight, lbits, hist, state, d->D,
                        d->H, d->W, p.Ns, d->ignore);
@@ -414,17 +346,14 @@ int ssbev_ohem_ce_bwd(const float* logits, const uint8_t* label, const float* cl
   if (ws_bytes < ssbev_ohem_ce_bwd_workspace(d)) return SSBEV_EWORKSPACE;
   hipStream_t st = as_stream(stream);
   const OhPlan p = oh_plan(d);
-  if (!d->upsample) {
-    hipLaunchKernelGGL(ohem_bwd_kernel<false>, dim3(oh_voxel_grid(p.N)), dim3(OH_T), 0, st, logits, label, class_weight, mask,
-                       inv_wsum, grad_out, grad_logits, d->D, d->H, d->W, p.Ns, (long)p.N);
-    return ssbev_launch_status();
-  }
-  float* gfine = static_cast<float*>(ws);
-  hipLaunchKernelGGL(ohem_bwd_kernel<true>, dim3(oh_voxel_grid(p.N)), dim3(OH_T), 0, st, logits, label, class_weight, mask,
-                     inv_wsum, grad_out, gfine, d->D, d->H, d->W, p.Ns, (long)p.N);
-  ssbev_upsample_dims u = {d->B, d->D, d->H, d->W, NC};
-  const int rc = ssbev_trilinear2x_bwd(gfine, grad_logits, &u, stream);
-  return rc != SSBEV_OK ? rc : ssbev_launch_status();
+  float* gfine = d->upsample ? static_cast<float*>(ws) : grad_logits;
+  if (!d->upsample)
+    hipLaunchKernelGGL(ohem_bwd_kernel<false>, dim3(voxel_grid(p.N)), dim3(OH_T), 0, st, logits, label, class_weight, mask,
+                       inv_wsum, grad_out, gfine, d->D, d->H, d->W, p.Ns, (long)p.N);
+  else
+    hipLaunchKernelGGL(ohem_bwd_kernel<true>, dim3(voxel_grid(p.N)), dim3(OH_T), 0, st, logits, label, class_weight, mask,
+                       inv_wsum, grad_out, gfine, d->D, d->H, d->W, p.Ns, (long)p.N);
+  return finish_fine_grad(gfine, grad_logits, d->B, d->D, d->H, d->W, stream);
 }
 
 }  // extern "C"
