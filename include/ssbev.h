@@ -142,6 +142,31 @@ size_t ssbev_gwc_warp_bwd_workspace(const ssbev_gwc_dims* d);
 int ssbev_gwc_warp_bwd_fused(const float* grad_vol, const float* left, const float* right,
                              const float* calib, float* grad_left, float* grad_right,
                              const ssbev_gwc_dims* d, void* workspace, size_t ws_bytes, ssbev_stream_t stream);
+/* Host-side plan query (since ssbev_version() 116; no device work): the kernel, block, plane chunks and dynamic LDS a launch of
+ * these dims uses, from the plan functions the launchers and ssbev_gwc_warp_bwd_workspace themselves read.  SSBEV_EINVAL for a
+ * NULL argument and for dims every entry point refuses (C % G, C % 4, a group width outside 1 / 2 / 4 / 8, down != 1); otherwise
+ * SSBEV_OK, and *_rc is what the entry point answers for these dims before anything is launched (SSBEV_OK, or SSBEV_EINVAL
+ * when no kernel fits the row into 160 KB of LDS: the other fields of that group are 0 then).
+ *   fwd_kernel: 1 = gwc_warp_fwd_kernel (a row per workgroup, 16-plane blocks: fwd_start holds multiples of 16 and is filled
+ *               for up to SSBEV_GWC_MAX_CHUNKS blocks), 4 = gwc_warp_fwd4_kernel, 5 = gwc_warp_fwd5_kernel.  fwd_px = pixels
+ *               of a tile (5) / of a pass over the row (4) / the row (1); fwd_tiles = tiles per row (1 for kernels 1 and 4).
+ *   bwd_kernel (ssbev_gwc_warp_bwd_fused): 1 = the two launches of gwc_warp_bwd_kernel (no plane chunks: one chunk [0, D);
+ *               bwd_threads is the block of each, 32-pixel tiles), 2 = gwc_warp_bwd2_kernel, 3 = gwc_warp_bwd3_kernel.
+ *   direct_* : ssbev_gwc_warp_bwd, always the two launches.
+ * Chunk c covers the planes [start[c], start[c + 1]). */
+#define SSBEV_GWC_MAX_CHUNKS 48
+typedef struct {
+  int fwd_rc, fwd_kernel, fwd_threads, fwd_px, fwd_tiles, fwd_nchunks;
+  int fwd_start[SSBEV_GWC_MAX_CHUNKS + 1];
+  size_t fwd_lds;
+  int bwd_rc, bwd_kernel, bwd_threads, bwd_nchunks;
+  int bwd_start[SSBEV_GWC_MAX_CHUNKS + 1];
+  size_t bwd_lds;
+  size_t bwd_workspace;          /* bytes, what ssbev_gwc_warp_bwd_workspace returns: 2 nchunks B H W C floats, 0 for one chunk */
+  int direct_rc, direct_threads;
+  size_t direct_lds;
+} ssbev_gwc_plan;
+int ssbev_gwc_plan_query(const ssbev_gwc_dims* d, ssbev_gwc_plan* out);
 
 /* ------------------------------------------------------------------------------------------
  * Dense N-d convolution family on MFMA (implicit GEMM, no im2col), channels-last fp32.

@@ -35,6 +35,17 @@ class GwcDims(C.Structure):
                 ("down", C.c_float), ("align_corners", C.c_int)]
 
 
+GWC_MAX_CHUNKS = 48
+
+
+class GwcPlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("fwd_rc", "fwd_kernel", "fwd_threads", "fwd_px", "fwd_tiles", "fwd_nchunks")] + \
+        [("fwd_start", C.c_int * (GWC_MAX_CHUNKS + 1)), ("fwd_lds", C.c_size_t)] + \
+        [(n, C.c_int) for n in ("bwd_rc", "bwd_kernel", "bwd_threads", "bwd_nchunks")] + \
+        [("bwd_start", C.c_int * (GWC_MAX_CHUNKS + 1)), ("bwd_lds", C.c_size_t), ("bwd_workspace", C.c_size_t),
+         ("direct_rc", C.c_int), ("direct_threads", C.c_int), ("direct_lds", C.c_size_t)]
+
+
 class ConvDims(C.Structure):
     _fields_ = [(n, C.c_int) for n in (
         "B", "Cin", "Cout", "Di", "Hi", "Wi", "Do", "Ho", "Wo", "kd", "kh", "kw", "sd", "sh", "sw",
@@ -165,6 +176,7 @@ SIGNATURES = {
     "ssbev_gwc_warp_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(GwcDims), _P]),
     "ssbev_gwc_warp_bwd_workspace": (C.c_size_t, [C.POINTER(GwcDims)]),
     "ssbev_gwc_warp_bwd_fused": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(GwcDims), _P, C.c_size_t, _P]),
+    "ssbev_gwc_plan_query": (C.c_int, [C.POINTER(GwcDims), C.POINTER(GwcPlan)]),
     "ssbev_conv_packed_weight_elems": (C.c_size_t, [C.POINTER(ConvDims)]),
     "ssbev_conv_kernel_class": (C.c_int, [C.POINTER(ConvDims), C.c_int]),
     "ssbev_conv_chunk_groups": (C.c_int, [C.POINTER(ConvDims), C.c_int]),

@@ -29,7 +29,7 @@ const char* ssbev_env(const char* name) {
 }
 
 extern "C" {
-int ssbev_version(void) { return 115; /* 0.1.15: + ssbev_imgseg_ce_* */ }
+int ssbev_version(void) { return 116; /* 0.1.16: + ssbev_gwc_plan_query */ }
 const char* ssbev_build_arch(void) { return "gfx950"; }
 
 // Forget every switch read so far: the next use of a name reads the environment again.  (Switches that a launch helper folded

@@ -33,8 +33,15 @@ struct XTap { int x0; float w0, w1; };
 
 // grid_sample coordinate un-normalisation (ATen grid_sampler_unnormalize)
 __device__ __forceinline__ float unnormalise(float coord, int size, int align_corners) {
-  return align_corners ? __fmul_rn(__fdiv_rn(__fadd_rn(coord, 1.0f), 2.0f), (float)(size - 1))
-                       : __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(coord, 1.0f), (float)size), 1.0f), 2.0f);
+  // hipcc's __fmul_rn / __fsub_rn are plain * and - that the compiler fuses: (coord + 1) * size - 1 became one fma, and the
+  // coordinate of the align_corners = 0 convention differed from grid_sample's by an ulp (a tap weight by 4e-6 at ix ~ 40).
+  // The pragma covers operators written in this block only, so the product and the difference are written out here.
+#pragma clang fp contract(off)
+  const float c1 = coord + 1.0f;
+  if (align_corners) return __fdiv_rn(c1, 2.0f) * (float)(size - 1);
+  const float prod = c1 * (float)size;
+  const float diff = prod - 1.0f;
+  return __fdiv_rn(diff, 2.0f);
 }
 
 __device__ __forceinline__ XTap depth_tap(float calib, int k, int D, float down, int align_corners) {
@@ -47,7 +54,8 @@ __device__ __forceinline__ XTap depth_tap(float calib, int k, int D, float down,
   t.x0 = (int)fminf(fmaxf(fl, -2.0f), (float)D + 1.0f);
   t.w1 = __fsub_rn(ix, fl);
   t.w0 = __fsub_rn(1.0f, t.w1);
-  if (!(ix == ix)) { t.x0 = -2; t.w0 = t.w1 = 0.0f; }
+  // a non-finite coordinate (NaN, or +-inf from an infinite / overflowing calibration: w1 = inf - inf) samples nothing
+  if (!(fabsf(ix) <= 3.402823466e+38f)) { t.x0 = -2; t.w0 = t.w1 = 0.0f; }
   return t;
 }
 
@@ -884,34 +892,44 @@ int env_int(const char* name, int dflt) {
 }
 
 // ---- forward: fwd4 (four groups per lane, run-cached correlations) when G % 4 == 0, else the per-plane kernel
-template <int CPG>
-int launch_fwd(const float* l, const float* r, const float* calib, float* vol, const ssbev_gwc_dims* d,
-               hipStream_t st) {
+// The one place that picks the forward kernel, its block, tiles, plane chunks and LDS: launch_fwd launches what it says and
+// ssbev_gwc_plan_query reports it.
+constexpr int FWD_MAXTHREADS = 512;                 // __launch_bounds__ of fwd4 / fwd5
+constexpr size_t LDS_LIMIT = 160 * 1024;
+enum { GWC_FWD_PLANE = 1, GWC_FWD_4 = 4, GWC_FWD_5 = 5 };
+struct FwdPlan {
+  int rc, kernel, threads, px, ntiles, rows, nt;   // rows: fwd4 rows per workgroup (0 = one LDS-staged row)
+  long groups;                                      // grid.x
+  PlaneChunks ch;                                   // fwd4 / fwd5 (the per-plane kernel walks fixed blocks of KCHUNK planes)
+  size_t lds;
+};
+
+FwdPlan plan_fwd(const ssbev_gwc_dims* d) {
   static const int variant = env_int("SSBEV_GWC_FWD", 3);          // 1 = per-plane kernel (r1), 2 = fwd4 (r2), 3 = fwd5
-  if (variant >= 3 && d->G % 4 == 0) {
+  FwdPlan p = {};
+  p.rc = SSBEV_OK;
+  int unit = 64;                                    // fwd4 / fwd5 block: a multiple of the wave and of G / 4 (see the kernels)
+  const int g4 = d->G / 4;
+  if (d->G % 4 == 0)
+    while (unit % g4 != 0) unit += 64;
+  // unit > FWD_MAXTHREADS (G / 4 with an odd part above 8: G = 36, 44, 52, 60, 72, ...): no legal block, per-plane kernel
+  const bool quads = d->G % 4 == 0 && unit <= FWD_MAXTHREADS;
+  if (variant >= 3 && quads) {
     static const int threads = env_int("SSBEV_GWC_FWD_THREADS", 256);
     static const int wg_target = env_int("SSBEV_GWC_FWD_WGS", 480);
     static const int nt = env_int("SSBEV_GWC_FWD_NT", 0);
     static const float run_cost = (float)env_int("SSBEV_GWC_FWD_RUNCOST", 4);
-    int unit = 64, g4 = d->G / 4;                   // block size: a multiple of the wave and of G / 4
-    while (unit % g4 != 0) unit += 64;
-    const int nthreads = std::max(unit, std::min(512, std::max(64, threads)) / unit * unit);
+    const int nthreads = std::max(unit, std::min(FWD_MAXTHREADS, std::max(64, threads)) / unit * unit);
     const int px = nthreads / g4, ntiles = (int)cdiv(d->W, px);
     const long groups = (long)d->B * d->H * ntiles;
-    const PlaneChunks ch = make_chunks(d->D, (int)cdiv(wg_target, groups), run_cost, d->D);
     const size_t lds = (size_t)d->W * (d->C + 4) * 4 + (size_t)d->D * sizeof(XTap);
-    if (lds <= 160 * 1024 && groups <= 0x7fffffffL) {
-      auto kern = nt ? gwc_warp_fwd5_kernel<CPG, true> : gwc_warp_fwd5_kernel<CPG, false>;
-      if (lds > 64 * 1024 &&
-          hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-              hipSuccess)
-        return SSBEV_ELAUNCH;
-      hipLaunchKernelGGL(kern, dim3((unsigned)groups, ch.n), dim3(nthreads), lds, st, l, r, calib, vol, ch, d->B, d->C,
-                         d->G, d->D, d->H, d->W, d->down, d->align_corners, ntiles);
-      return ssbev_launch_status();
+    if (lds <= LDS_LIMIT && groups <= 0x7fffffffL) {
+      p.kernel = GWC_FWD_5; p.threads = nthreads; p.px = px; p.ntiles = ntiles; p.groups = groups; p.nt = nt; p.lds = lds;
+      p.ch = make_chunks(d->D, (int)cdiv(wg_target, groups), run_cost, d->D);
+      return p;
     }
   }
-  if (variant != 1 && d->G % 4 == 0) {
+  if (variant != 1 && quads) {
     static const int threads = env_int("SSBEV_GWC_FWD_THREADS", 256);
     static const int wg_target = env_int("SSBEV_GWC_FWD_WGS", 768);
     static const int nt = env_int("SSBEV_GWC_FWD_NT", 1);
@@ -921,39 +939,88 @@ int launch_fwd(const float* l, const float* r, const float* calib, float* vol, c
     while (rows > 1 && d->H % rows != 0) --rows;                         // a workgroup's rows share one batch element
     const int nrow_groups = rows > 0 ? d->B * d->H / rows : d->B * d->H;
     const PlaneChunks ch = make_chunks(d->D, (int)cdiv(wg_target, nrow_groups), run_cost, FWD_MAXLEN);
+    int longest = 0;
+    for (int i = 0; i < ch.n; ++i) longest = std::max(longest, ch.start[i + 1] - ch.start[i]);
     const size_t lds = (rows > 0 ? 0 : (size_t)d->W * (d->C + 4) * 4) + FWD_MAXLEN * sizeof(XTap);
-    if (lds <= 160 * 1024) {
-      auto kern = rows > 0 ? (nt ? gwc_warp_fwd4_kernel<CPG, true, false> : gwc_warp_fwd4_kernel<CPG, false, false>)
-                           : (nt ? gwc_warp_fwd4_kernel<CPG, true, true> : gwc_warp_fwd4_kernel<CPG, false, true>);
-      if (lds > 64 * 1024 &&
-          hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-              hipSuccess)
-        return SSBEV_ELAUNCH;
-      int unit = 64, g4 = d->G / 4;                 // block size: a multiple of the wave and of G / 4 (see the kernel)
-      while (unit % g4 != 0) unit += 64;
-      const int nthreads = std::max(unit, std::min(512, std::max(64, threads)) / unit * unit);
-      hipLaunchKernelGGL(kern, dim3(nrow_groups, ch.n), dim3(nthreads), lds, st, l, r, calib,
-                         vol, ch, d->B, d->C, d->G, d->D, d->H, d->W, d->down, d->align_corners, std::max(rows, 1));
-      return ssbev_launch_status();
+    // (MAX_CHUNKS chunks of more than FWD_MAXLEN planes, D > 1536: the kernel's tap array would not hold a chunk)
+    if (lds <= LDS_LIMIT && longest <= FWD_MAXLEN) {
+      p.kernel = GWC_FWD_4; p.rows = rows; p.nt = nt; p.lds = lds; p.ch = ch; p.groups = nrow_groups;
+      p.threads = std::max(unit, std::min(FWD_MAXTHREADS, std::max(64, threads)) / unit * unit);
+      p.px = p.threads / g4; p.ntiles = 1;
+      return p;
     }
   }
-  const size_t lds = fwd_lds_bytes(d);
-  if (lds > 160 * 1024) return SSBEV_EINVAL;
+  p.kernel = GWC_FWD_PLANE; p.threads = 256; p.px = d->W; p.ntiles = 1; p.groups = (long)d->B * d->H;
+  p.lds = fwd_lds_bytes(d);
+  if (p.lds > LDS_LIMIT) { p = FwdPlan{}; p.rc = SSBEV_EINVAL; }
+  return p;
+}
+
+template <int CPG>
+int launch_fwd(const float* l, const float* r, const float* calib, float* vol, const ssbev_gwc_dims* d,
+               hipStream_t st) {
+  const FwdPlan p = plan_fwd(d);
+  if (p.rc != SSBEV_OK) return p.rc;
+  const size_t lds = p.lds;
+  if (p.kernel == GWC_FWD_5) {
+    auto kern = p.nt ? gwc_warp_fwd5_kernel<CPG, true> : gwc_warp_fwd5_kernel<CPG, false>;
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+            hipSuccess)
+      return SSBEV_ELAUNCH;
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.groups, p.ch.n), dim3(p.threads), lds, st, l, r, calib, vol, p.ch, d->B, d->C,
+                       d->G, d->D, d->H, d->W, d->down, d->align_corners, p.ntiles);
+    return ssbev_launch_status();
+  }
+  if (p.kernel == GWC_FWD_4) {
+    auto kern = p.rows > 0 ? (p.nt ? gwc_warp_fwd4_kernel<CPG, true, false> : gwc_warp_fwd4_kernel<CPG, false, false>)
+                           : (p.nt ? gwc_warp_fwd4_kernel<CPG, true, true> : gwc_warp_fwd4_kernel<CPG, false, true>);
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+            hipSuccess)
+      return SSBEV_ELAUNCH;
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.groups, p.ch.n), dim3(p.threads), lds, st, l, r, calib,
+                       vol, p.ch, d->B, d->C, d->G, d->D, d->H, d->W, d->down, d->align_corners, std::max(p.rows, 1));
+    return ssbev_launch_status();
+  }
   auto kern = gwc_warp_fwd_kernel<CPG>;
   if (lds > 64 * 1024 &&
       hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
           hipSuccess)
     return SSBEV_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3(d->B * d->H, cdiv(d->D, KCHUNK)), dim3(256), lds, st, l, r, calib, vol, d->B, d->C,
+  hipLaunchKernelGGL(kern, dim3((unsigned)p.groups, cdiv(d->D, KCHUNK)), dim3(p.threads), lds, st, l, r, calib, vol, d->B, d->C,
                      d->G, d->D, d->H, d->W, d->down, d->align_corners);
   return ssbev_launch_status();
+}
+
+// The one place that picks the backward realisation, its block, plane chunks, LDS and workspace: the launchers launch what it
+// says, ssbev_gwc_warp_bwd_workspace returns its workspace and ssbev_gwc_plan_query reports it.
+enum { GWC_BWD_TWO_LAUNCH = 1, GWC_BWD_2 = 2, GWC_BWD_3 = 3 };
+struct BwdPlan {
+  int rc, kernel, threads, unr, nt;
+  PlaneChunks ch;                                   // two-launch: one chunk [0, D) (every thread walks all planes)
+  size_t lds, workspace;
+};
+
+BwdPlan plan_bwd(const ssbev_gwc_dims* d) {         // ssbev_gwc_warp_bwd: the two launches of gwc_warp_bwd_kernel
+  BwdPlan p = {};
+  p.lds = bwd_lds_bytes(d);
+  if (p.lds > LDS_LIMIT) { p = BwdPlan{}; p.rc = SSBEV_EINVAL; return p; }
+  p.rc = SSBEV_OK;
+  p.kernel = GWC_BWD_TWO_LAUNCH;
+  // one thread per (pixel, source group) of the tile: the 192-plane walk is the only serial loop left
+  // (whole waves: an odd G gave 288, 352, ... threads; the item -> (pixel, group) map does not depend on the block)
+  p.threads = std::min(1024, std::max(256, (int)cdiv(WTILE * d->G, 64) * 64));
+  p.ch.n = 1; p.ch.start[0] = 0; p.ch.start[1] = d->D;
+  return p;
 }
 
 template <int CPG>
 int launch_bwd(const float* gvol, const float* l, const float* r, const float* calib, float* gl, float* gr,
                const ssbev_gwc_dims* d, hipStream_t st) {
-  const size_t lds = bwd_lds_bytes(d);
-  if (lds > 160 * 1024) return SSBEV_EINVAL;
+  const BwdPlan p = plan_bwd(d);
+  if (p.rc != SSBEV_OK) return p.rc;
+  const size_t lds = p.lds;
   auto kl = gwc_warp_bwd_kernel<CPG, true>;
   auto kr = gwc_warp_bwd_kernel<CPG, false>;
   if (lds > 64 * 1024) {
@@ -963,8 +1030,7 @@ int launch_bwd(const float* gvol, const float* l, const float* r, const float* c
             hipSuccess)
       return SSBEV_ELAUNCH;
   }
-  // one thread per (pixel, source group) of the tile: the 192-plane walk is the only serial loop left
-  dim3 grid(d->B * d->H, cdiv(d->W, WTILE)), block(std::min(1024, std::max(256, WTILE * d->G)));
+  dim3 grid(d->B * d->H, cdiv(d->W, WTILE)), block(p.threads);
   hipLaunchKernelGGL(kl, grid, block, lds, st, gvol, r, calib, gl, d->B, d->C, d->G, d->D, d->H, d->W, d->down,
                      d->align_corners);
   hipLaunchKernelGGL(kr, grid, block, lds, st, gvol, l, calib, gr, d->B, d->C, d->G, d->D, d->H, d->W, d->down,
@@ -973,49 +1039,64 @@ int launch_bwd(const float* gvol, const float* l, const float* r, const float* c
 }
 
 // ---- fused backward (one read of the gradient volume) ------------------------------------------------------------
-struct Bwd2Plan { bool ok; int threads; PlaneChunks ch; size_t lds; };
+inline int bwd_maxi(int cpg) { return cpg >= 8 ? BwdCfg<8>::MAXI : cpg == 4 ? BwdCfg<4>::MAXI : BwdCfg<1>::MAXI; }
 
-template <int CPG>
-Bwd2Plan plan_bwd2(const ssbev_gwc_dims* d) {
-  Bwd2Plan p;
-  p.ok = false;
-  if (d->G % 4 != 0 || d->G > 64 || 64 % d->G != 0) return p;
+BwdPlan plan_bwd_fused(const ssbev_gwc_dims* d) {   // ssbev_gwc_warp_bwd_fused
+  if (d->G % 4 != 0 || d->G > 64 || 64 % d->G != 0) return plan_bwd(d);
+  const int cpg = d->C / d->G, maxi = bwd_maxi(cpg);
   const int items = d->W * d->G;
-  int threads = (int)cdiv(cdiv(items, BwdCfg<CPG>::MAXI), 64) * 64;
+  int threads = (int)cdiv(cdiv(items, maxi), 64) * 64;
   threads = std::max(threads, (int)cdiv(cdiv(items / 4, BWD_MAXQ), 64) * 64);
   threads = std::max(threads, 256);
-  if (threads > BWD_MAXTHREADS) return p;
+  if (threads > BWD_MAXTHREADS) return plan_bwd(d);
+  BwdPlan p = {};
+  p.rc = SSBEV_OK;
   p.threads = threads;
   p.lds = (size_t)2 * d->W * (d->C + 4) * 4 + (size_t)2 * d->W * d->G * 4 + (size_t)d->D * sizeof(BTap) +
           (size_t)d->G * MAX_SRC * 8 + (size_t)d->G * 16 + 16;
-  if (p.lds > 160 * 1024) return p;
+  if (p.lds > LDS_LIMIT) return plan_bwd(d);
   static const int wg_target = env_int("SSBEV_GWC_BWD_WGS", 256);     // one workgroup per CU (LDS-bound occupancy)
   const int rows = d->B * d->H;
   static const float run_cost = (float)env_int("SSBEV_GWC_BWD_RUNCOST", 8);
   p.ch = make_chunks(d->D, std::max(1, wg_target / rows), run_cost, d->D);
-  p.ok = true;
+  if (p.ch.n > 1) p.workspace = (size_t)2 * p.ch.n * d->B * d->H * d->W * d->C * sizeof(float);
+  static const int variant = env_int("SSBEV_GWC_BWD", 3);           // 2 = bwd2 (r2), 3 = bwd3
+  static const int unr = env_int("SSBEV_GWC_BWD_UNR", variant >= 3 ? 1 : 2), nt = env_int("SSBEV_GWC_BWD_NT", 0);
+  p.unr = unr; p.nt = nt;
+  // bwd3 has no tails (KITTI: 640 threads).  The first and third condition give threads = W G / 8 and MAXI = 8: group widths 1
+  // and 2 only (MAXI is 4 / 2 for widths 4 / 8), which is why gwc_warp_bwd3_kernel is instantiated for those two alone.
+  const bool exact = maxi == 8 && d->W * (d->G / 4) == BWD_MAXQ * threads && threads % d->G == 0 &&
+                     maxi * (threads / d->G) == d->W;
+  p.kernel = variant >= 3 && exact ? GWC_BWD_3 : GWC_BWD_2;
   return p;
+}
+
+typedef void (*Bwd3Kernel)(const float*, const float*, const float*, const float*, float*, float*, PlaneChunks, int, int, int,
+                           int, int, int, float, int);
+template <int CPG>
+Bwd3Kernel bwd3_instance(int unr) {
+  if constexpr (CPG <= 2) return unr >= 2 ? gwc_warp_bwd3_kernel<CPG, 2> : gwc_warp_bwd3_kernel<CPG, 1>;   // 4 planes per batch spill
+  else return nullptr;                                 // plan_bwd_fused never answers GWC_BWD_3 for these widths
 }
 
 template <int CPG>
 int launch_bwd2(const float* gvol, const float* l, const float* r, const float* calib, float* gl, float* gr,
                 const ssbev_gwc_dims* d, void* ws, size_t ws_bytes, hipStream_t st) {
-  const Bwd2Plan p = plan_bwd2<CPG>(d);
-  if (!p.ok) return launch_bwd<CPG>(gvol, l, r, calib, gl, gr, d, st);
+  const BwdPlan p = plan_bwd_fused(d);
+  if (p.rc != SSBEV_OK) return p.rc;
+  if (p.kernel == GWC_BWD_TWO_LAUNCH) return launch_bwd<CPG>(gvol, l, r, calib, gl, gr, d, st);
   const size_t slab = (size_t)d->B * d->H * d->W * d->C;
   float *pl = gl, *pr = gr;
   if (p.ch.n > 1) {
-    if (!ws || ws_bytes < 2 * p.ch.n * slab * sizeof(float)) return SSBEV_EWORKSPACE;
+    if (!ws || ws_bytes < p.workspace) return SSBEV_EWORKSPACE;
     pl = static_cast<float*>(ws);
     pr = pl + p.ch.n * slab;
   }
-  static const int variant = env_int("SSBEV_GWC_BWD", 3);           // 2 = bwd2 (r2), 3 = bwd3
-  static const int unr = env_int("SSBEV_GWC_BWD_UNR", variant >= 3 ? 1 : 2), nt = env_int("SSBEV_GWC_BWD_NT", 0);
+  const int unr = p.unr, nt = p.nt;
   const dim3 grid(d->B * d->H, p.ch.n), block(p.threads);
-  const bool exact = d->W * (d->G / 4) == BWD_MAXQ * p.threads && p.threads % d->G == 0 &&
-                     BwdCfg<CPG>::MAXI * (p.threads / d->G) == d->W;       // bwd3 has no tails (KITTI: 640 threads)
-  if (variant >= 3 && exact) {
-    auto kern = unr >= 2 ? gwc_warp_bwd3_kernel<CPG, 2> : gwc_warp_bwd3_kernel<CPG, 1>;   // 4 planes per batch spill
+  if (p.kernel == GWC_BWD_3) {
+    const Bwd3Kernel kern = bwd3_instance<CPG>(unr);
+    if (!kern) return SSBEV_EINVAL;
     if (p.lds > 64 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds) !=
             hipSuccess)
@@ -1037,13 +1118,6 @@ int launch_bwd2(const float* gvol, const float* l, const float* r, const float* 
     hipLaunchKernelGGL(gwc_partial_reduce_kernel, dim3(cdiv(n4, 256), 2), dim3(256), 0, st, pl, gl, pr, gr, p.ch.n, n4);
   }
   return ssbev_launch_status();
-}
-
-template <int CPG>
-size_t bwd2_workspace(const ssbev_gwc_dims* d) {
-  const Bwd2Plan p = plan_bwd2<CPG>(d);
-  if (!p.ok || p.ch.n <= 1) return 0;
-  return (size_t)2 * p.ch.n * d->B * d->H * d->W * d->C * sizeof(float);
 }
 
 }  // namespace
@@ -1077,12 +1151,36 @@ int ssbev_gwc_warp_bwd(const float* grad_vol, const float* left, const float* ri
 
 size_t ssbev_gwc_warp_bwd_workspace(const ssbev_gwc_dims* d) {
   if (!gwc_dims_ok(d)) return 0;
-  switch (d->C / d->G) {
-    case 1: return bwd2_workspace<1>(d);
-    case 2: return bwd2_workspace<2>(d);
-    case 4: return bwd2_workspace<4>(d);
-    default: return bwd2_workspace<8>(d);
+  return plan_bwd_fused(d).workspace;
+}
+
+int ssbev_gwc_plan_query(const ssbev_gwc_dims* d, ssbev_gwc_plan* out) {
+  static_assert(SSBEV_GWC_MAX_CHUNKS == MAX_CHUNKS, "ssbev.h and the chunk planner disagree");
+  if (!out || !gwc_dims_ok(d)) return SSBEV_EINVAL;
+  *out = ssbev_gwc_plan{};
+  const FwdPlan f = plan_fwd(d);
+  out->fwd_rc = f.rc;
+  if (f.rc == SSBEV_OK) {
+    out->fwd_kernel = f.kernel; out->fwd_threads = f.threads; out->fwd_px = f.px; out->fwd_tiles = f.ntiles; out->fwd_lds = f.lds;
+    if (f.kernel == GWC_FWD_PLANE) {
+      out->fwd_nchunks = (int)cdiv(d->D, KCHUNK);
+      for (int c = 0; c <= std::min(out->fwd_nchunks, MAX_CHUNKS); ++c) out->fwd_start[c] = std::min(c * KCHUNK, d->D);
+    } else {
+      out->fwd_nchunks = f.ch.n;
+      for (int c = 0; c <= f.ch.n; ++c) out->fwd_start[c] = f.ch.start[c];
+    }
   }
+  const BwdPlan b = plan_bwd_fused(d);
+  out->bwd_rc = b.rc;
+  if (b.rc == SSBEV_OK) {
+    out->bwd_kernel = b.kernel; out->bwd_threads = b.threads; out->bwd_nchunks = b.ch.n; out->bwd_lds = b.lds;
+    out->bwd_workspace = b.workspace;
+    for (int c = 0; c <= b.ch.n; ++c) out->bwd_start[c] = b.ch.start[c];
+  }
+  const BwdPlan t = plan_bwd(d);
+  out->direct_rc = t.rc;
+  if (t.rc == SSBEV_OK) { out->direct_threads = t.threads; out->direct_lds = t.lds; }
+  return SSBEV_OK;
 }
 
 int ssbev_gwc_warp_bwd_fused(const float* grad_vol, const float* left, const float* right, const float* calib,
