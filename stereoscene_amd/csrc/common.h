@@ -30,6 +30,34 @@ static inline const char* ssbev_tune(const char* name) { return ssbev_env(name);
 static inline const char* ssbev_tune(const char*) { return nullptr; }
 #endif
 
+// XCD-aware remap of a 1-D workgroup order.  Hardware deals workgroup L of n to XCD L % 8, and each XCD has its own L2.  The
+// logical order 0 .. n-1 is cut into 8 contiguous ranges, one per XCD (the first n % 8 of them one longer), and workgroup L
+// takes entry L / 8 of its XCD's range: consecutive LOGICAL ids -- the workgroups a kernel wants to share operands -- run on
+// one XCD and meet in its L2.  Kernels call it as xcd_chunk_id(blockIdx.x, gridDim.x) (or on a flattened 2-D / 3-D grid).
+__host__ __device__ constexpr unsigned xcd_chunk_id(unsigned L, unsigned n) {
+  const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
+  const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+  return base + (L >> 3);
+}
+// ... is a permutation of 0 .. n-1: every n up to 64 and one n of each residue mod 8 above 256, checked by the compiler.
+constexpr bool xcd_chunk_id_permutes(unsigned n) {
+  bool seen[272] = {};
+  for (unsigned L = 0; L < n; ++L) {
+    const unsigned id = xcd_chunk_id(L, n);
+    if (id >= n || seen[id]) return false;
+    seen[id] = true;
+  }
+  return true;
+}
+constexpr bool xcd_chunk_id_checked() {
+  for (unsigned n = 1; n <= 64; ++n)
+    if (!xcd_chunk_id_permutes(n)) return false;
+  for (unsigned n = 257; n <= 264; ++n)
+    if (!xcd_chunk_id_permutes(n)) return false;
+  return true;
+}
+static_assert(xcd_chunk_id_checked(), "xcd_chunk_id must map 0 .. n-1 onto itself");
+
 // 64-lane butterfly sum (all lanes receive the total).
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

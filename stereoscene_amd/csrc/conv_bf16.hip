@@ -100,9 +100,7 @@ conv_gather16_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp
   {
     const unsigned n = gridDim.x * gridDim.y;
     const unsigned L = blockIdx.x + gridDim.x * blockIdx.y;
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const unsigned Lp = base + (L >> 3);
+    const unsigned Lp = xcd_chunk_id(L, n);
     bx = (int)(Lp / gridDim.y);
     by = (int)(Lp % gridDim.y);
   }
@@ -305,13 +303,7 @@ conv_tap16_kernel(const bf16_t* __restrict__ X, const uint4* __restrict__ wp, co
     for (int j = 0; j < 2; ++j) wb[tt][j] = wp[((wave * 7 + tt) * 2 + j) * 64 + lane];
   const int ntap = wave < 3 ? 7 : 6;
 
-  unsigned chunk_id;
-  {
-    const unsigned n = gridDim.x, L = blockIdx.x;
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    chunk_id = base + (L >> 3);
-  }
+  const unsigned chunk_id = xcd_chunk_id(blockIdx.x, gridDim.x);
   const int seg = chunk_id % g.nseg, range = chunk_id / g.nseg;
   const int w0 = seg * kT16Wseg;
   const int g_begin = range * g.gpc, g_end = min(g.NG, g_begin + g.gpc);
@@ -478,9 +470,7 @@ conv_wide16_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ wp, 
   int mtile, ntile;
   {   // XCD-aware order: the column tiles of one voxel tile, then neighbouring voxel tiles, share an L2
     const unsigned n = gridDim.x, L = blockIdx.x;
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const unsigned Lp = base + (L >> 3);
+    const unsigned Lp = xcd_chunk_id(L, n);
     mtile = (int)(Lp / g.ntn); ntile = (int)(Lp % g.ntn);
   }
   int t = mtile;
@@ -642,13 +632,8 @@ wgrad16_kernel(const bf16_t* __restrict__ P, const bf16_t* __restrict__ Q, float
   const int li = lane & 31, lk = lane >> 5;
   // 1-D grid in the XCD-aware order [chunk group][channel tiles][tap groups]: the workgroups that read the SAME voxel chunk (one
   // per channel tile and tap group) are neighbours on one XCD -- the chunk comes from HBM once and from that L2 afterwards
-  unsigned Lp;
-  {
-    const unsigned n = gridDim.x, L = blockIdx.x;
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    Lp = g.xcd_order ? base + (L >> 3) : L;
-  }
+  const unsigned Lx = xcd_chunk_id(blockIdx.x, gridDim.x);
+  unsigned Lp = g.xcd_order ? Lx : blockIdx.x;
   const int kw_groups = (g.kw + TW - 1) / TW, kh_groups = (g.kh + TH - 1) / TH;
   const unsigned ztiles = (unsigned)(g.kd * kh_groups * kw_groups);
   const int nqt = (g.Cq + 32 * MQ - 1) / (32 * MQ);
@@ -827,9 +812,7 @@ wgrad_ring16_kernel(const bf16_t* __restrict__ P, const bf16_t* __restrict__ Q, 
   int chunk = blockIdx.x, cqt = 0, cpg = 0, kdz = 0;
   if (!NARROW && g.xcd_order) {
     const unsigned n = gridDim.x, L = blockIdx.x;
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    unsigned Lp = base + (L >> 3);
+    unsigned Lp = xcd_chunk_id(L, n);
     kdz = (int)(Lp % 3u); Lp /= 3u;
     cqt = (int)(Lp % (unsigned)g.ncqt); Lp /= (unsigned)g.ncqt;
     const unsigned ncpg = (unsigned)((g.Cp + 127) / 128);
@@ -1067,9 +1050,7 @@ conv_igemm16_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp,
   int mb, nb, bt;
   {
     const unsigned n = gridDim.x, L = blockIdx.x;
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    unsigned Lp = base + (L >> 3);
+    unsigned Lp = xcd_chunk_id(L, n);
     nb = (int)(Lp % (unsigned)nblocks); Lp /= (unsigned)nblocks;
     mb = (int)(Lp % (unsigned)mblocks);
     bt = (int)(Lp / (unsigned)mblocks);
@@ -1752,9 +1733,7 @@ gemm16_tn_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bm, fl
   int kt, nt, slice, bt;
   {
     const unsigned n = gridDim.x, L = blockIdx.x;
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    unsigned Lp = base + (L >> 3);
+    unsigned Lp = xcd_chunk_id(L, n);
     const unsigned tiles = (unsigned)(ktiles * ntiles);
     const unsigned t = Lp % tiles; Lp /= tiles;
     slice = (int)(Lp % (unsigned)nslices);

@@ -117,9 +117,7 @@ conv_gather_kernel(const float* __restrict__ x, const float* __restrict__ wp, co
   {
     const unsigned n = gridDim.x * gridDim.y;
     const unsigned L = blockIdx.x + gridDim.x * blockIdx.y;
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const unsigned Lp = base + (L >> 3);
+    const unsigned Lp = xcd_chunk_id(L, n);
     bx = (int)(Lp / gridDim.y);
     by = (int)(Lp % gridDim.y);
   }
@@ -874,9 +872,7 @@ conv_igemm_kernel(const float* __restrict__ x, const float* __restrict__ wp, con
   int mb, nb;
   {
     const unsigned n = gridDim.x, L = blockIdx.x;
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const unsigned Lp = base + (L >> 3);
+    const unsigned Lp = xcd_chunk_id(L, n);
     nb = (int)(Lp % (unsigned)nblocks);
     mb = (int)(Lp / (unsigned)nblocks);
   }
@@ -1252,9 +1248,7 @@ wgrad_cf_kernel(const float* __restrict__ Pt, const float* __restrict__ Qp, floa
   {
     const unsigned per = gridDim.y * gridDim.z, n = gridDim.x * per;
     const unsigned L = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const unsigned Lp = base + (L >> 3);
+    const unsigned Lp = xcd_chunk_id(L, n);
     bx = Lp / per;
     byy = (Lp % per) % gridDim.y;
     bz = (Lp % per) / gridDim.y;
@@ -1527,9 +1521,7 @@ wgrad_lds_kernel(const float* __restrict__ Pg, const float* __restrict__ Qg, flo
   {   // XCD-aware remap: the workgroups that walk the SAME chunk (other channel tiles / kd) share one L2
     const unsigned per = gridDim.y * gridDim.z, n = gridDim.x * per;
     const unsigned L = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const unsigned Lp = base + (L >> 3);
+    const unsigned Lp = xcd_chunk_id(L, n);
     bx = Lp / per;
     byy = (Lp % per) % gridDim.y;
     bz = (Lp % per) / gridDim.y;
@@ -2069,13 +2061,7 @@ conv_tap_kernel(const float* __restrict__ X, const float* __restrict__ wp, const
   }
   const int ntap = wave < 3 ? 7 : 6;
 
-  unsigned chunk_id;
-  {   // XCD-aware remap: the five w-segments of a row range share one L2
-    const unsigned n = gridDim.x, L = blockIdx.x;
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    chunk_id = base + (L >> 3);
-  }
+  const unsigned chunk_id = xcd_chunk_id(blockIdx.x, gridDim.x);   // XCD-aware remap: the five w-segments of a row range share one L2
   const int seg = chunk_id % g.nseg, range = chunk_id / g.nseg;
   const int w0 = seg * kTapWseg;
   const int g_begin = range * g.gpc, g_end = min(g.NG, g_begin + g.gpc);
@@ -2304,13 +2290,7 @@ conv_taph_kernel(const float* __restrict__ X, const float* __restrict__ wp, cons
 #pragma unroll
     for (int r = 0; r < 8; ++r) wr[c][r] = wp[((wave * 9 + c) * 8 + r) * 64 + lane];
 
-  unsigned chunk_id;
-  {
-    const unsigned n = gridDim.x, L = blockIdx.x;
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    chunk_id = base + (L >> 3);
-  }
+  const unsigned chunk_id = xcd_chunk_id(blockIdx.x, gridDim.x);
   const int seg = chunk_id % g.nseg, range = chunk_id / g.nseg;
   const int H2 = g.H >> 1;
   const int g_begin = range * g.gpc, g_end = min(g.NG, g_begin + g.gpc);
@@ -2554,13 +2534,7 @@ conv_tapdh_kernel(const float* __restrict__ X, const float* __restrict__ wp, con
 #pragma unroll
     for (int r = 0; r < 16; ++r) wr[c][r] = wp[((wave * 3 + c) * 16 + r) * 64 + lane];
 
-  unsigned chunk_id;
-  {
-    const unsigned n = gridDim.x, L = blockIdx.x;
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    chunk_id = base + (L >> 3);
-  }
+  const unsigned chunk_id = xcd_chunk_id(blockIdx.x, gridDim.x);
   const int seg = chunk_id % g.nseg, range = chunk_id / g.nseg;
   const int H2 = g.H >> 1, D2 = g.D >> 1;
   const int g_begin = range * g.gpc, g_end = min(g.NG, g_begin + g.gpc);
@@ -2856,13 +2830,7 @@ wgrad_tapdh_kernel(const float* __restrict__ X, const float* __restrict__ GY, fl
   const int li = lane & 31, lk = lane >> 5;
   const int fd = wave >> 2, fh = wave & 3;
 
-  unsigned chunk_id;
-  {
-    const unsigned n = gridDim.x, L = blockIdx.x;
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    chunk_id = base + (L >> 3);
-  }
+  const unsigned chunk_id = xcd_chunk_id(blockIdx.x, gridDim.x);
   const int seg = chunk_id % g.nseg, range = chunk_id / g.nseg;
   const int H2 = g.H >> 1, D2 = g.D >> 1;
   const int g_begin = range * g.gpc, g_end = min(g.NG, g_begin + g.gpc);
@@ -3216,13 +3184,7 @@ conv_tap2_kernel(const float* __restrict__ X, const float* __restrict__ wp, cons
     for (int r = 0; r < 16; ++r) wr[tt][r] = wp[((wave * 7 + tt) * 16 + r) * 64 + lane];
   const int ntap = tg < 3 ? 7 : 6;
 
-  unsigned chunk_id;
-  {
-    const unsigned n = gridDim.x, L = blockIdx.x;
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    chunk_id = base + (L >> 3);
-  }
+  const unsigned chunk_id = xcd_chunk_id(blockIdx.x, gridDim.x);
   const int seg = chunk_id % g.nseg, range = chunk_id / g.nseg;
   const int w0 = seg * 16;                   // first output voxel of the segment; its first source voxel is 2 w0 - 1
   const int g_begin = range * g.gpc, g_end = min(g.NG, g_begin + g.gpc);
@@ -3468,13 +3430,7 @@ conv_tap2up_kernel(const float* __restrict__ X, const float* __restrict__ wp, co
   }
   ntap = __builtin_amdgcn_readfirstlane(ntap);
 
-  unsigned chunk_id;
-  {
-    const unsigned n = gridDim.x, L = blockIdx.x;
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    chunk_id = base + (L >> 3);
-  }
+  const unsigned chunk_id = xcd_chunk_id(blockIdx.x, gridDim.x);
   const int seg = chunk_id % g.nseg, range = chunk_id / g.nseg;
   const int c0 = seg * 16;                   // first coarse cell of the segment
   const int g_begin = range * g.gpc, g_end = min(g.NG, g_begin + g.gpc);
@@ -3630,13 +3586,7 @@ wgrad_thin_kernel(const float* __restrict__ X, const float* __restrict__ GY, flo
   float* gyl = tl + kTapRingF;               // [2 buffers][32 voxels][NP]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  unsigned chunk_id;
-  {
-    const unsigned n = gridDim.x, L = blockIdx.x;
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    chunk_id = base + (L >> 3);
-  }
+  const unsigned chunk_id = xcd_chunk_id(blockIdx.x, gridDim.x);
   const int seg = chunk_id % g.nseg, range = chunk_id / g.nseg;
   const int w0 = seg * kTapWseg;
   const int g_begin = range * g.gpc, g_end = min(g.NG, g_begin + g.gpc);
@@ -3801,13 +3751,7 @@ conv_thin_kernel(const float* __restrict__ X, const float* __restrict__ wt, cons
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   for (int i = tid; i < 27 * kThinNP * 32; i += 256) wl[i] = wt[i];
-  unsigned chunk_id;
-  {
-    const unsigned n = gridDim.x, L = blockIdx.x;
-    const unsigned xcd = L & 7, q = n >> 3, r = n & 7;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    chunk_id = base + (L >> 3);
-  }
+  const unsigned chunk_id = xcd_chunk_id(blockIdx.x, gridDim.x);
   const int seg = chunk_id % g.nseg, range = chunk_id / g.nseg;
   const int w0 = seg * kTapWseg;
   const int g_begin = range * g.gpc, g_end = min(g.NG, g_begin + g.gpc);

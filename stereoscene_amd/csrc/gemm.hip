@@ -69,11 +69,6 @@ __global__ void gemm_d2s_rowoff_kernel(long* __restrict__ rowoff, int M, int D, 
   rowoff[m] = ((((long)bb * (D * kd) + (long)d * kd) * (H * kh) + (long)h * kh) * (W * kw) + (long)w * kw) * Co;
 }
 
-__device__ __forceinline__ int xcd_logical(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
 // ---------------------------------------------------------------------------------------------------------------- NN / NT
 // BT = false: B is [K][N] (NN);  BT = true: B is [N][K] (NT).  D2S: 0 = plain, 1 = NN scatters its C rows, 2 = NT gathers its A rows.
 // MW = 32-row tiles per wave along M: 2 (workgroup tile 128 rows) or 3 (192 rows: the BRI products have M = D = 192 rows, on
@@ -101,7 +96,7 @@ gemm_nn_kernel(const float* __restrict__ A, const float* __restrict__ B, const f
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, lk = lane >> 5;
   const int wm = wave / WGN, wn = wave % WGN;
-  int id = xcd_logical(blockIdx.x, gridDim.x);
+  int id = (int)xcd_chunk_id(blockIdx.x, gridDim.x);
   const int nb = id % g.nblocks; id /= g.nblocks;
   const int mb = id % g.mblocks; id /= g.mblocks;
   const int chunk = id % g.nchunk;                 // split-K: k stages [st_begin, st_end) of this chunk
@@ -275,7 +270,7 @@ gemm_tn_kernel(const float* __restrict__ A, const float* __restrict__ B, float* 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, lk = lane >> 5;
   const int wk = wave / WGN, wn = wave % WGN;
-  int id = xcd_logical(blockIdx.x, gridDim.x);
+  int id = (int)xcd_chunk_id(blockIdx.x, gridDim.x);
   const int nb = id % g.nblocks; id /= g.nblocks;
   const int kb = id % g.mblocks; id /= g.mblocks;
   const int chunk = id % g.nchunk;

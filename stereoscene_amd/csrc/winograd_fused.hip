@@ -81,8 +81,7 @@ wino_df_kernel(const float* __restrict__ P, const float* __restrict__ Wp, float*
   // ---- task decode.  Hardware deals consecutive workgroup ids round-robin over the 8 XCDs; the logical task list
   // (xi_hw slowest, row task u, column group fastest) is cut into 8 contiguous ranges, one per XCD: an XCD works through
   // whole frequencies (their weight slab and P planes meet in ITS L2), adjacent depth tiles / column groups run back to back.
-  const int nwg = gridDim.x, xq = nwg >> 3, xr = nwg & 7, xcd = blockIdx.x & 7;
-  const int logical = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (blockIdx.x >> 3);
+  const int logical = (int)xcd_chunk_id(blockIdx.x, gridDim.x);
   const int cg = logical % g.ncolgrp, u = (logical / g.ncolgrp) % g.NU, xhw = logical / (g.ncolgrp * g.NU);
   const int i = u % g.ND, tg = (u / g.ND) % g.nrowgrp, b = u / (g.ND * g.nrowgrp);
   const int t0 = tg * BM;
@@ -343,8 +342,7 @@ wino_dfw_kernel(const float* __restrict__ P, const float* __restrict__ Z, float*
   const int kw = wave % KW, nw = wave / KW;
   // XCD-aware order: consecutive LOGICAL ids (column blocks / K blocks of one row chunk: they share the P and Z slabs) run
   // on one XCD and meet in its L2; hardware deals consecutive workgroup ids round-robin over the 8 XCDs
-  const int nwg = gridDim.x, xq = nwg >> 3, xr = nwg & 7, xcd = blockIdx.x & 7;
-  int id = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (blockIdx.x >> 3);
+  int id = (int)xcd_chunk_id(blockIdx.x, gridDim.x);
   const int nb = id % g.nnb; id /= g.nnb;
   const int kb = id % g.nkb; id /= g.nkb;
   const int chunk = id % g.nchunk;
