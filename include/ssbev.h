@@ -624,6 +624,48 @@ int ssbev_frustum_dist_bwd(const float* logits, const uint8_t* ids, const float*
 int ssbev_frustum_labels(const uint8_t* labels, uint8_t* ids, int32_t* counts, int X, int Y, int Z, const float* params,
                          int img_h, int img_w, int frustum_size, ssbev_stream_t stream);
 
+/* 3-D context relation prior (since version 117): the operators of CPMegaVoxels (occupancy/backbones/crp3d.py:217-262 of the
+ * reference), its loss compute_super_CP_multilabel_loss (resnet3d.py:269-290) and its label step (voxel_labels.py:79-174).
+ * The relation grid is [X, Y, Z] with N = X Y Z row voxels; its 2 x 2 x 2 blocks are the Mc = N / 8 mega voxels, numbered
+ * (x / 2) (Y / 2) (Z / 2) + (y / 2) (Z / 2) + z / 2.  The four relations of a (row voxel, mega voxel) pair: 0 a child of the mega
+ * voxel has the row's non-empty class, 1 a child has another non-empty class and the row is non-empty, 2 row and a child are both
+ * empty (0), 3 exactly one of row and child is empty; children labelled 255 are skipped and a row labelled 255 has no positive.
+ *   logits    [B, N, 4, Mc] fp32: the channels-last result of the four context_prior_logits convolutions run as one layer
+ *   labels    [B, X, Y, Z] uint8: the down-sampled label grid (ssbev_label_downsample); the [4, N, Mc] matrix is never built
+ *   loss      one float (device): mean over all 4 B N Mc elements of -[pw_r y log s(x) + (1 - y) log(1 - s(x))], s = sigmoid, in
+ *             the softplus form (finite for any x); pw_r = (B N Mc - cnt_r) / cnt_r with cnt_r the positives of relation r over
+ *             the whole batch, and 1 when cnt_r = 0 (it then multiplies nothing; the reference divides by zero and returns NaN)
+ *   pos_weight  [4] float (device), kept by the caller for backward
+ *   backward  grad_logits [B, N, 4, Mc] = grad_out[0] * d loss / d logits (grad_out: one float on the device)
+ * Per-workgroup sums in double, folded in a fixed order: no float atomics, nothing read back, every run gives the same bits.
+ * SSBEV_EINVAL before any device work: NULL pointers, non-positive or odd X / Y / Z, N >= 2^24;  SSBEV_EWORKSPACE: ws_bytes below
+ * the query, which answers 0 for refused dims. */
+typedef struct { int B, X, Y, Z; } ssbev_crp_dims;
+size_t ssbev_crp_loss_workspace(const ssbev_crp_dims* d);
+int ssbev_crp_loss_fwd(const float* logits, const uint8_t* labels, float* loss, float* pos_weight, const ssbev_crp_dims* d, void* ws,
+                       size_t ws_bytes, ssbev_stream_t stream);
+int ssbev_crp_loss_bwd(const float* logits, const uint8_t* labels, const float* pos_weight, const float* grad_out,
+                       float* grad_logits, const ssbev_crp_dims* d, ssbev_stream_t stream);
+/* CreateRelationLabels._downsample_label on the device, byte-exact: labels [X, Y, Z] uint8 -> out [X / ds, Y / ds, Z / ds].  A
+ * block with more than 0.95 ds^3 (in double, compared with >) voxels labelled 0 or 255 becomes 0 when the zeros outnumber the
+ * 255s and 255 otherwise (also on a tie); any other block takes its most frequent class 1 .. 254, the lowest id on a tie.
+ * SSBEV_EINVAL: NULL pointers, non-positive dims, downscale outside 1..32 or not a divisor of X, Y and Z, X Y Z >= 2^31. */
+int ssbev_label_downsample(const uint8_t* labels, uint8_t* out, int X, int Y, int Z, int downscale, ssbev_stream_t stream);
+/* Relation gather: out[b][n][r C2 + c] = sum_m sigmoid(logits[b][n][r][m]) context[b][m][c], one fp32 MFMA GEMM per (b, r) with
+ * the sigmoid applied while the A operand is staged; sigmoid(logits) is never written.
+ *   logits    [B, N, R, Mc];  context [B, Mc, C2] (the channels-last mega-context volume)
+ *   out       row n of sample b starts at out + (b N + n) ld_out: pass the address of the first context channel of the
+ *             concatenated [input, context] tensor and its channel count as ld_out (>= R C2)
+ *   backward  grad_out laid out as out;  grad_logits [B, N, R, Mc] = (grad_out_r context^T) s (1 - s);
+ *             grad_context [B, Mc, C2] = sum_r s_r^T grad_out_r, the reduction cut into slices folded in a fixed order (ws)
+ * SSBEV_EINVAL: NULL pointers, non-positive dims, R > 16, ld_out < R C2;  SSBEV_EWORKSPACE: ws_bytes below the query. */
+typedef struct { int B, N, Mc, C2, R; int64_t ld_out; } ssbev_crp_gather_dims;
+int ssbev_crp_gather_fwd(const float* logits, const float* context, float* out, const ssbev_crp_gather_dims* d,
+                         ssbev_stream_t stream);
+size_t ssbev_crp_gather_bwd_workspace(const ssbev_crp_gather_dims* d);
+int ssbev_crp_gather_bwd(const float* logits, const float* context, const float* grad_out, float* grad_logits, float* grad_context,
+                         const ssbev_crp_gather_dims* d, void* ws, size_t ws_bytes, ssbev_stream_t stream);
+
 /* Running statistics of a training-mode BatchNorm from the (mean, rstd) ssbev_groupnorm_fwd returned with G == C over the
  * batch: running_mean <- (1-m) running_mean + m mean; running_var <- (1-m) running_var + m var n/(n-1)
  * (torch.nn.BatchNorm3d as built at ViewTransformerLSSVoxel.py:83-88; n = elements per channel). */

@@ -109,6 +109,14 @@ class FrustumDims(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("B", "D", "H", "W", "C", "F", "upsample")]
 
 
+class CrpDims(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("B", "X", "Y", "Z")]
+
+
+class CrpGatherDims(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("B", "N", "Mc", "C2", "R")] + [("ld_out", C.c_int64)]
+
+
 class GemmDims(C.Structure):
     _fields_ = [("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("batch", C.c_int),
                 ("lda", C.c_int64), ("ldb", C.c_int64), ("ldc", C.c_int64), ("sa", C.c_int64), ("sb", C.c_int64), ("sc", C.c_int64),
@@ -336,6 +344,13 @@ SIGNATURES = {
     "ssbev_frustum_dist_bwd_workspace": (C.c_size_t, [C.POINTER(FrustumDims)]),
     "ssbev_frustum_dist_bwd": (C.c_int, [_P] * 5 + [C.POINTER(FrustumDims), _P, C.c_size_t, _P]),
     "ssbev_frustum_labels": (C.c_int, [_P] * 3 + [C.c_int] * 3 + [_P] + [C.c_int] * 3 + [_P]),
+    "ssbev_crp_loss_workspace": (C.c_size_t, [C.POINTER(CrpDims)]),
+    "ssbev_crp_loss_fwd": (C.c_int, [_P] * 4 + [C.POINTER(CrpDims), _P, C.c_size_t, _P]),
+    "ssbev_crp_loss_bwd": (C.c_int, [_P] * 5 + [C.POINTER(CrpDims), _P]),
+    "ssbev_label_downsample": (C.c_int, [_P, _P] + [C.c_int] * 4 + [_P]),
+    "ssbev_crp_gather_fwd": (C.c_int, [_P] * 3 + [C.POINTER(CrpGatherDims), _P]),
+    "ssbev_crp_gather_bwd_workspace": (C.c_size_t, [C.POINTER(CrpGatherDims)]),
+    "ssbev_crp_gather_bwd": (C.c_int, [_P] * 5 + [C.POINTER(CrpGatherDims), _P, C.c_size_t, _P]),
     "ssbev_occ_dice_tail": (C.c_int, [_P, C.c_float, _P, _P, _P]),
     "ssbev_lga_weights": (C.c_int, [_P, _P] + [C.c_int] * 4 + [_P]),
     "ssbev_occ_lga_workspace": (C.c_size_t, [C.POINTER(UpsampleDims)]),

@@ -2615,6 +2615,212 @@ def frustum_labels(labels, view, point_cloud_range, frustum_size=8):
     return ids, counts.view(fs * fs, 20)
 
 
+# -------------------------------------------------------------------------------------------------
+# 3-D context relation prior (csrc/crp.hip): label down-sampling, relation matrix, relation loss, relation gather
+# -------------------------------------------------------------------------------------------------
+CRP = os.environ.get("SSBEV_CRP", "1") != "0"                # fused relation loss and gather (0 = the tensor forms: sigmoid, bmm, cat, BCEWithLogits)
+CRP_RELATIONS = 4
+
+
+def label_downsample(labels, downscale):
+    """``CreateRelationLabels._downsample_label`` (voxel_labels.py:79-122), byte-exact: labels uint8 [X,Y,Z] -> uint8
+    [X/ds, Y/ds, Z/ds].  A block with more than ``0.95 * ds**3`` voxels labelled 0 or 255 becomes 0 when the zeros outnumber the
+    255s and 255 otherwise (a tie included); any other block takes its most frequent class 1..254, the lowest id on a tie.
+    CUDA labels run ``ssbev_label_downsample``; CPU labels the same rule in tensor ops."""
+    ds = int(downscale)
+    lab = torch.as_tensor(labels)
+    if lab.dim() != 3 or lab.dtype != torch.uint8:
+        raise ValueError(f"label_downsample: uint8 [X,Y,Z] expected, got {lab.dtype} {tuple(lab.shape)}")
+    X, Y, Z = (int(v) for v in lab.shape)
+    if not 1 <= ds <= 32 or X % ds or Y % ds or Z % ds:
+        raise ValueError(f"label_downsample: downscale {downscale} must be in 1..32 and divide the grid {(X, Y, Z)}")
+    if lab.is_cuda:
+        lib = capi.load()
+        lab = lab.contiguous()
+        out = torch.empty(X // ds, Y // ds, Z // ds, dtype=torch.uint8, device=lab.device)
+        capi.check(lib.ssbev_label_downsample(capi.ptr(lab), capi.ptr(out), X, Y, Z, ds, capi.stream()), "ssbev_label_downsample")
+        return out
+    blocks = lab.view(X // ds, ds, Y // ds, ds, Z // ds, ds).permute(0, 2, 4, 1, 3, 5).reshape(-1, ds ** 3).long()
+    hist = torch.zeros(blocks.shape[0], 256, dtype=torch.int64).scatter_add_(1, blocks, torch.ones_like(blocks))
+    z0, z255 = hist[:, 0], hist[:, 255]
+    empty = (z0 + z255).double() > 0.95 * ds * ds * ds
+    ids = torch.arange(1, 255)
+    cls = ids[(hist[:, 1:255] * 256 + (255 - ids)).argmax(1)]                     # the larger count, then the lower id
+    out = torch.where(empty, torch.where(z0 > z255, torch.zeros_like(cls), torch.full_like(cls, 255)), cls)
+    return out.to(torch.uint8).view(X // ds, Y // ds, Z // ds)
+
+
+def relation_matrix(labels):
+    """``CreateRelationLabels.compute_CP_mega_matrix(is_binary=False)`` (voxel_labels.py:124-174): the down-sampled label grid
+    uint8 [X,Y,Z] (or [B,X,Y,Z]) -> the dense relation matrix uint8 [4, N, Mc] ([B, 4, N, Mc]); N = X Y Z rows in grid order, Mc
+    = N / 8 columns, column ``xx (Y/2)(Z/2) + yy (Z/2) + zz`` for the 2x2x2 block at (2xx, 2yy, 2zz).  Entry [r, n, m] is the OR
+    over the block's children that are not 255 of: 0 child == row != 0; 1 child != row, both != 0; 2 child == row == 0; 3 child !=
+    row and one of them 0; rows labelled 255 are all zero.  Tensor ops on the labels' device."""
+    lab = torch.as_tensor(labels)
+    g = (lab if lab.dim() == 4 else lab[None]).long()
+    B, X, Y, Z = g.shape
+    if X % 2 or Y % 2 or Z % 2:
+        raise ValueError(f"relation_matrix: the grid {(X, Y, Z)} must be even on every axis")
+    row = g.reshape(B, -1, 1, 1)
+    kids = g.view(B, X // 2, 2, Y // 2, 2, Z // 2, 2).permute(0, 1, 3, 5, 2, 4, 6).reshape(B, 1, -1, 8)
+    ok = (kids != 255) & (row != 255)
+    same = kids == row
+    rels = (same & (kids != 0), ~same & (kids != 0) & (row != 0), same & (kids == 0), ~same & ((kids == 0) | (row == 0)))
+    m = torch.stack([(r & ok).any(-1) for r in rels], dim=1).to(torch.uint8)
+    return m if lab.dim() == 4 else m[0]
+
+
+def relation_loss_tensor(P_logits, matrices):
+    """``compute_super_CP_multilabel_loss`` (resnet3d.py:269-290) in tensor ops on any device, in the logits' dtype, without a
+    read-back: P_logits [B, 4, Mc, N], matrices [B, 4, N, Mc] (0 / 1).  pos_weight_r = negatives / positives of relation r over
+    the batch; for a relation without a positive the reference divides by zero and returns NaN, here the weight is 1 (it
+    multiplies nothing)."""
+    x = P_logits.permute(0, 1, 3, 2)
+    y = matrices.to(device=x.device)
+    if tuple(y.shape) != tuple(x.shape):
+        raise ValueError(f"relation loss: matrices {tuple(y.shape)} do not match the logits' {tuple(x.shape)} ([B, R, N, Mc])")
+    R = x.shape[1]
+    pos = y.long().sum(dim=(0, 2, 3))
+    neg = y.numel() // R - pos
+    pw = torch.where(pos > 0, neg.double() / pos.clamp(min=1).double(), torch.ones_like(pos, dtype=torch.float64))
+    return torch.nn.functional.binary_cross_entropy_with_logits(x, y.to(x.dtype), pos_weight=pw.to(x.dtype).view(1, R, 1, 1))
+
+
+def relation_loss_supported(P_logits, labels):
+    """The fused relation loss serves fp32 logits [B, 4, Mc, N] on the GPU with uint8 labels [B, X, Y, Z] on the same device, an
+    even grid, N = X Y Z and Mc = N / 8."""
+    if not (torch.is_tensor(P_logits) and torch.is_tensor(labels) and P_logits.is_cuda and P_logits.dtype == torch.float32):
+        return False
+    if P_logits.dim() != 4 or labels.dim() != 4 or labels.dtype != torch.uint8 or labels.device != P_logits.device:
+        return False
+    B, R, Mc, N = P_logits.shape
+    X, Y, Z = (int(v) for v in labels.shape[1:])
+    return (R == CRP_RELATIONS and labels.shape[0] == B and X % 2 == 0 and Y % 2 == 0 and Z % 2 == 0 and N == X * Y * Z
+            and Mc * 8 == N and N < (1 << 24))
+
+
+class _RelationLoss(torch.autograd.Function):
+    """P_logits [B,4,Mc,N] (a view of the channels-last convolution result [B,N,4,Mc]: no copy), labels uint8 [B,X,Y,Z] -> the
+    relation loss (0-dim fp32), ``ssbev_crp_loss_fwd / _bwd``.  The four pos_weights stay on the device for backward."""
+
+    @staticmethod
+    def forward(ctx, P_logits, labels):
+        lib = capi.load()
+        pcl = P_logits.permute(0, 3, 1, 2).contiguous()
+        lab = labels.contiguous()
+        B, X, Y, Z = lab.shape
+        d = capi.CrpDims(B, X, Y, Z)
+        dev = pcl.device
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        pw = torch.empty(CRP_RELATIONS, dtype=torch.float32, device=dev)
+        ws = _ws(lib.ssbev_crp_loss_workspace(C.byref(d)), dev)
+        with _span("crp", 0.0, 4.0 * pcl.numel() + lab.numel(), "fwd   crp_loss"):
+            capi.check(lib.ssbev_crp_loss_fwd(capi.ptr(pcl), capi.ptr(lab), capi.ptr(loss), capi.ptr(pw), C.byref(d), capi.ptr(ws),
+                                              ws.numel(), capi.stream()), "ssbev_crp_loss_fwd")
+        ctx.save_for_backward(pcl, lab, pw)
+        ctx.dims = d
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = capi.load()
+        pcl, lab, pw = ctx.saved_tensors
+        gl = gout.to(torch.float32).reshape(1).contiguous()
+        gp = torch.empty_like(pcl)
+        with _span("crp", 0.0, 8.0 * pcl.numel() + lab.numel(), "bwd   crp_loss"):
+            capi.check(lib.ssbev_crp_loss_bwd(capi.ptr(pcl), capi.ptr(lab), capi.ptr(pw), capi.ptr(gl), capi.ptr(gp), C.byref(ctx.dims),
+                                              capi.stream()), "ssbev_crp_loss_bwd")
+        return gp.permute(0, 2, 3, 1), None
+
+
+def relation_loss(P_logits, labels=None, matrices=None):
+    """The context-prior relation loss of ``P_logits`` [B, 4, Mc, N]: the mean over all 4 B N Mc elements of the weighted binary
+    cross entropy against the relation matrix, pos_weight pooled over the batch (``relation_loss_tensor``); fp32, 0-dim.
+    ``labels``: the down-sampled label grid uint8 [B,X,Y,Z] -- on the GPU with ``CRP`` on the fused kernel derives every matrix
+    bit from it and the dense matrix is never built; elsewhere the matrix is expanded (``relation_matrix``) for the tensor form.
+    ``matrices``: a dense [B, 4, N, Mc] matrix from the caller takes precedence and always runs the TENSOR form."""
+    if matrices is not None:
+        return relation_loss_tensor(P_logits, torch.as_tensor(matrices)).float()
+    if labels is None:
+        raise ValueError("relation_loss needs the down-sampled labels or the dense relation matrices")
+    labels = torch.as_tensor(labels).to(device=P_logits.device, dtype=torch.uint8)
+    if CRP and relation_loss_supported(P_logits, labels):
+        return _RelationLoss.apply(P_logits, labels)
+    return relation_loss_tensor(P_logits, relation_matrix(labels)).float()
+
+
+def relation_gather_tensor(P_logits, context, x=None):
+    """The gather of ``CPMegaVoxels.forward`` (crp3d.py:229-253) as the reference writes it: per relation sigmoid, permute and
+    ``bmm`` with the mega context, ``cat`` of the results (and of ``x`` in front)."""
+    B, R, Mc, N = P_logits.shape
+    rels = [torch.bmm(torch.sigmoid(P_logits[:, r].permute(0, 2, 1)), context) for r in range(R)]
+    out = torch.cat(rels, dim=2).permute(0, 2, 1)
+    return out if x is None else torch.cat([x.reshape(B, -1, N), out], dim=1)
+
+
+def relation_gather_supported(P_logits, context, x=None):
+    ts = [P_logits, context] + ([x] if x is not None else [])
+    if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in ts):
+        return False
+    if P_logits.dim() != 4 or context.dim() != 3 or context.shape[:2] != (P_logits.shape[0], P_logits.shape[2]):
+        return False
+    B, R, Mc, N = P_logits.shape
+    return R <= 16 and max(N, Mc, context.shape[2]) < (1 << 24) and (x is None or (x.shape[0] == B and x[0, 0].numel() == N))
+
+
+class _RelationGather(torch.autograd.Function):
+    """out[b, Cin + r C2 + c, n] = sum_m sigmoid(P[b,r,m,n]) context[b,m,c] behind the Cin channels of ``x``: one MFMA GEMM per
+    (b, r) that stages sigmoid(P) into LDS and writes its channel slice of the concatenated channels-last tensor
+    (``ssbev_crp_gather_fwd / _bwd``).  sigmoid(P) is never stored; backward recomputes it."""
+
+    @staticmethod
+    def forward(ctx, P_logits, context, x):
+        lib = capi.load()
+        pcl = P_logits.permute(0, 3, 1, 2).contiguous()               # [B,N,R,Mc]: the layout the convolution left
+        cx = context.contiguous()
+        B, N, R, Mc = pcl.shape
+        C2 = cx.shape[2]
+        cin = 0 if x is None else x.shape[1]
+        ctot = cin + R * C2
+        out = torch.empty(B, N, ctot, dtype=torch.float32, device=pcl.device)
+        if x is not None:
+            out[:, :, :cin].copy_(x.reshape(B, cin, N).permute(0, 2, 1))
+        d = capi.CrpGatherDims(B, N, Mc, C2, R, ctot)
+        with _span("crp", 2.0 * B * R * N * Mc * C2, 4.0 * (pcl.numel() + B * N * R * C2), "fwd   crp_gather"):
+            capi.check(lib.ssbev_crp_gather_fwd(capi.ptr(pcl), capi.ptr(cx), C.c_void_p(out.data_ptr() + 4 * cin), C.byref(d),
+                                                capi.stream()), "ssbev_crp_gather_fwd")
+        ctx.save_for_backward(pcl, cx)
+        ctx.dims, ctx.cin, ctx.xshape = d, cin, (None if x is None else tuple(x.shape))
+        return out.permute(0, 2, 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = capi.load()
+        pcl, cx = ctx.saved_tensors
+        d, cin = ctx.dims, ctx.cin
+        gcl = g.permute(0, 2, 1).contiguous()                          # [B,N,Ctot]
+        gp = torch.empty_like(pcl)
+        gc = torch.empty_like(cx)
+        ws = _ws(lib.ssbev_crp_gather_bwd_workspace(C.byref(d)), pcl.device)
+        with _span("crp", 4.0 * d.B * d.R * d.N * d.Mc * d.C2, 4.0 * (2 * pcl.numel() + 2 * d.B * d.N * d.R * d.C2) + 2.0 * ws.numel(),
+                   "bwd   crp_gather"):
+            capi.check(lib.ssbev_crp_gather_bwd(capi.ptr(pcl), capi.ptr(cx), C.c_void_p(gcl.data_ptr() + 4 * cin), capi.ptr(gp),
+                                                capi.ptr(gc), C.byref(d), capi.ptr(ws), ws.numel(), capi.stream()),
+                       "ssbev_crp_gather_bwd")
+        gx = None if ctx.xshape is None else gcl[:, :, :cin].permute(0, 2, 1).reshape(ctx.xshape)
+        return gp.permute(0, 2, 3, 1), gc, gx
+
+
+def relation_gather(P_logits, context, x=None):
+    """Context features gathered through the relation priors: P_logits [B, R, Mc, N], context [B, Mc, C2] (, x [B, Cin, ...] with
+    N positions) -> [B, (Cin +) R C2, N] with ``out[b, Cin + r C2 + c, n] = sum_m sigmoid(P[b,r,m,n]) context[b,m,c]`` and ``x`` in
+    the first Cin channels.  fp32 GPU tensors with ``CRP`` on run the fused HIP path (the result is a view of a channels-last
+    buffer); anything else the tensor form ``relation_gather_tensor``."""
+    if CRP and relation_gather_supported(P_logits, context, x):
+        return _RelationGather.apply(P_logits, context, x)
+    return relation_gather_tensor(P_logits, context, x)
+
+
 DEPTH_BCE = os.environ.get("SSBEV_DEPTH_BCE", "1") != "0"    # fused depth loss (0 = the ~35 ATen ops of the tensor expression)
 
 

@@ -152,6 +152,14 @@ class _HipBatchNorm:
 
     def forward(self, x, residual=None, relu=None):
         relu = self.fused_relu if relu is None else relu
+        if self.training and self.num_features % 4 != 0:
+            # channel counts the vectorised kernels do not take (the 2-channel bottleneck of a CPMegaVoxels(8, ...) test block; no
+            # layer of the model): the ATen operator, as GroupNorm does for its narrow case
+            run = self._running()
+            rm, rv, m = run if run is not None else (None, None, 0.0)
+            y = nn.functional.batch_norm(x, rm, rv, self.weight, self.bias, True, m, self.eps)
+            y = y if residual is None else y + residual
+            return torch.relu(y) if relu else y
         if self.training:
             y, mean, rstd = F.batch_norm_train(x, self.weight, self.bias, self.eps, residual, relu, running=self._running())
             return y

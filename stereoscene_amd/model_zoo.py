@@ -16,7 +16,7 @@ def image_branch_cfg(arch="b7"):
 
 def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False, loss_depth_type="bce", voxel_ohem=0.0,
               ohem_topk=0.25, frustum_dist=0.0, voxel_dice=0.0, voxel_lga=0.0, imgseg=False, loss_seg_weight=1.0,
-              lift_with_imgseg=False, imgseg_labels="img_seg"):
+              lift_with_imgseg=False, imgseg_labels="img_seg", crp3d=False, crp_level=2):
     """Same structure and hyper-parameters as the reference config's ``model`` dict for the sizes in ``cfg`` (a
     synthetic.CFG_*).  ``image_branch=False`` (default, the benchmarked hot path a1-a16) leaves the 2-D
     image backbone/neck out: the detector then takes the image-neck features in place of raw images.  ``loss_depth_type``:
@@ -29,12 +29,20 @@ def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False, 
     ``imgseg=True`` builds the view transformer's image-view segmentation head and adds ``loss_imgseg`` (weight
     ``loss_seg_weight``); the training call then needs the label map named by ``imgseg_labels`` ("img_seg", the reference's
     right-view map, or "img_seg_left").  ``lift_with_imgseg=True`` lifts the 20 class probabilities with the features: the 3-D
-    encoder then takes ``numC_Trans + 20`` channels."""
+    encoder then takes ``numC_Trans + 20`` channels.  ``crp3d=True`` builds the 3-D encoder's context relation prior behind stage
+    ``crp_level`` (on that stage's grid: ``crp_size``) and adds ``loss_rel_ce``; the training call then needs ``CP_mega_labels``
+    (pipelines.CreateRelationLabels(relations=True)) or a dense ``CP_mega_matrix``."""
     seg = dict(imgseg=True, imgseg_class=20, loss_seg_weight=float(loss_seg_weight), lift_with_imgseg=bool(lift_with_imgseg)) \
         if imgseg else {}
     bev_in = numC_Trans + (20 if imgseg and lift_with_imgseg else 0)
     norm_cfg = dict(type="GN", num_groups=32, requires_grad=True)
     channels = [128, 256, 512]
+    crp = {}
+    if crp3d:
+        if not 0 <= crp_level < len(channels):
+            raise ValueError(f"crp_level must name one of the {len(channels)} encoder stages, got {crp_level}")
+        # the encoder works on the lifted grid (occ_size / 2); stage i halves it i times
+        crp = dict(crp3d=True, crp_level=int(crp_level), crp_size=tuple(int(v) // (2 << crp_level) for v in cfg["occ_size"]))
     return dict(
         type="BEVDepthOccupancy", **(image_branch_cfg() if image_branch else {}),
         img_view_transformer=dict(
@@ -43,7 +51,7 @@ def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False, 
             data_config=dict(input_size=tuple(cfg["input_size"])), numC_Trans=numC_Trans, vp_megvii=False,
             warp_align_corners=warp_align_corners, loss_depth_type=loss_depth_type, **seg),
         img_bev_encoder_backbone=dict(type="CustomResNet3D", depth=18, num_stage=3, n_input_channels=bev_in,
-                                      block_inplanes=channels, out_indices=(0, 1, 2), norm_cfg=norm_cfg),
+                                      block_inplanes=channels, out_indices=(0, 1, 2), norm_cfg=norm_cfg, **crp),
         img_bev_encoder_neck=dict(type="SECONDFPN3D", norm_cfg=norm_cfg, in_channels=channels,
                                   upsample_strides=[1, 2, 4], out_channels=[128, 128, 128]),
         pts_bbox_head=dict(type="OccHead", num_level=1, in_channels=[384], out_channel=20, semantic_kitti=True,

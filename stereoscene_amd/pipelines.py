@@ -170,10 +170,15 @@ class CreateRelationLabels:
     The upstream step unpacks ``results['img_inputs'][:7]`` as ONE view and fails on this model's stereo input, where
     ``img_inputs`` is the tuple (left view, right view) (voxel_labels.py:252).  Here the LEFT view (``img_inputs[0]``) is used when
     ``img_inputs`` holds views, and ``img_inputs`` itself when its first entry is a tensor (the single-view layout the step was
-    written for).  The relation matrix of the same class (``compute_CP_mega_matrix``) is commented out upstream and not built;
+    written for).  ``relations=True`` (the upstream has these two calls commented out, voxel_labels.py:246-250, hence a flag) adds
+    ``CP_mega_labels`` (uint8 [X/ds, Y/ds, Z/ds], ds = ``relation_downscale``): the label grid ``_downsample_label`` produces,
+    byte-exact, on the GPU one kernel (``functional.label_downsample``).  The dense relation matrix ``compute_CP_mega_matrix``
+    builds from it (4 N Mc bytes that carry the grid's N bytes of information) is not stored: the relation loss derives its bits
+    from the grid, and ``functional.relation_matrix`` expands it for whoever wants the matrix.
     ``output_scale`` is accepted and, as upstream, unused."""
 
-    def __init__(self, point_cloud_range, grid_size, class_names, output_scale=2.0, dense_masks=False, device=None):
+    def __init__(self, point_cloud_range, grid_size, class_names, output_scale=2.0, dense_masks=False, device=None,
+                 relations=False, relation_downscale=8):
         self.grid_size = np.array(grid_size)
         self.point_cloud_range = np.array(point_cloud_range, dtype=np.float64)
         self.class_names, self.n_classes, self.output_scale = class_names, len(class_names), output_scale
@@ -181,6 +186,10 @@ class CreateRelationLabels:
             raise NotImplementedError("CreateRelationLabels is built for the 20 SemanticKITTI classes")
         self.dense_masks, self.device = bool(dense_masks), device
         self.frustum_size = 8
+        self.relations, self.relation_downscale = bool(relations), int(relation_downscale)
+        if self.relations and any(int(v) % (2 * self.relation_downscale) for v in self.grid_size):
+            raise ValueError(f"CreateRelationLabels: relations=True needs a grid {tuple(self.grid_size)} that is a multiple of "
+                             f"2 x relation_downscale = {2 * self.relation_downscale} on every axis")
 
     def __call__(self, results):
         from . import functional as F
@@ -195,6 +204,8 @@ class CreateRelationLabels:
         if self.dense_masks:
             f = torch.arange(self.frustum_size ** 2, device=ids.device, dtype=torch.uint8).view(-1, 1, 1, 1)
             results["frustums_masks"] = ids.unsqueeze(0) == f
+        if self.relations:
+            results["CP_mega_labels"] = F.label_downsample(lab.to(torch.uint8), self.relation_downscale)
         return results
 
 
@@ -698,7 +709,7 @@ class CustomSemanticKITTILssDataset:
 
 def collate(samples, device="cuda"):
     """Batch of pipeline outputs -> the detector's call signature: ``img_inputs = (left10, right10)`` with a leading
-    batch axis on every entry (what mmcv's collate + scatter produce upstream), ``gt_occ`` [B, X, Y, Z] int64; ``frustums_ids`` / ``frustums_class_dists`` / ``frustums_masks`` are stacked
+    batch axis on every entry (what mmcv's collate + scatter produce upstream), ``gt_occ`` [B, X, Y, Z] int64; ``frustums_ids`` / ``frustums_class_dists`` / ``frustums_masks`` / ``CP_mega_labels`` are stacked
     when every sample carries them, and so are ``img_seg`` / ``img_seg_left`` ([B, H, W] float, the labels of the image-view
     segmentation loss)."""
     on_gpu = torch.device(device).type == "cuda"
@@ -726,7 +737,7 @@ def collate(samples, device="cuda"):
         views.append(tuple(cols))
     gt = put(torch.stack([torch.as_tensor(s["gt_occ"]).long() for s in samples]))
     out = dict(img_inputs=tuple(views), gt_occ=gt)
-    for k in ("frustums_ids", "frustums_class_dists", "frustums_masks"):     # CreateRelationLabels' outputs, when every sample has them
+    for k in ("frustums_ids", "frustums_class_dists", "frustums_masks", "CP_mega_labels"):     # CreateRelationLabels' outputs, when every sample has them
         if all(k in s for s in samples):
             out[k] = put(torch.stack([torch.as_tensor(s[k]) for s in samples]))
     for k in ("img_seg", "img_seg_left"):                                   # CreateDepthFromLiDAR's label maps

@@ -79,12 +79,20 @@ class BEVDepthOccupancy(nn.Module):
         if with_seg and kwargs.get(self.imgseg_labels) is None:
             raise KeyError(f"imgseg=True needs the training kwarg {self.imgseg_labels!r} (pipelines.CreateDepthFromLiDAR + "
                            "collate provide it)")
+        bev = getattr(self, "img_bev_encoder_backbone", None)
+        with_crp = getattr(bev, "crp3d", False)
+        if with_crp and kwargs.get("CP_mega_labels") is None and kwargs.get("CP_mega_matrix") is None:
+            raise KeyError("crp3d=True needs the training kwarg 'CP_mega_labels' (pipelines.CreateRelationLabels(relations=True) + "
+                           "collate provide it) or a dense 'CP_mega_matrix'")
         voxel_feats, img_feats, depth = self.extract_feat(points, img=img_inputs, img_metas=img_metas)
         losses = {}
         if not self.disable_loss_depth:
             losses["loss_depth"] = self.img_view_transformer.get_depth_loss(img_inputs[0][7], depth)   # DET:230
         if with_seg:                                                                                   # DET:243-246
             losses["loss_imgseg"] = vt.get_seg_loss(kwargs[self.imgseg_labels])
+        if with_crp:                                                                                   # DET:238-241
+            losses["loss_rel_ce"] = bev.crp_loss(CP_mega_matrices=kwargs.get("CP_mega_matrix"),
+                                                 CP_mega_labels=kwargs.get("CP_mega_labels"))
         losses.update(self.forward_pts_train(voxel_feats, gt_occ, points_occ, img_metas, **kwargs))
         return losses
 

@@ -10,6 +10,7 @@ from .. import functional as F
 from ..layers import Conv3d, GroupNorm, build_conv_layer, build_norm_layer, build_upsample_layer, fuse_relu_, norm_pair
 from ..registry import BACKBONES, HEADS, NECKS
 from . import losses as L
+from .crp3d import CPMegaVoxels
 
 
 class BasicBlock3d(nn.Module):
@@ -38,19 +39,30 @@ class BasicBlock3d(nn.Module):
 class CustomResNet3D(nn.Module):
     def __init__(self, depth, block_inplanes=(64, 128, 256, 512), block_strides=(1, 2, 2, 2), out_indices=(0, 1, 2, 3),
                  num_stage=4, n_input_channels=3, shortcut_type="B", norm_cfg=dict(type="BN3d", requires_grad=True),
-                 crp3d=False, crp_level=2, widen_factor=1.0):
+                 crp3d=False, crp_level=2, widen_factor=1.0, crp_size=(32, 32, 4)):
+        """``crp3d=True`` builds the context relation prior ``CP_mega_voxels`` (crp3d.py:173-262) behind stage ``crp_level``
+        (resnet3d.py:158-165, 238-241).  ``crp_size``: the grid of that stage's output, which the reference hard-codes as
+        (32, 32, 4); a keyword here so that small grids can run."""
         super().__init__()
-        if depth not in (10, 18, 34) or crp3d or shortcut_type != "B":
-            raise NotImplementedError("only the BasicBlock / shortcut-B / no-CRP variants used by the config are built")
+        if depth not in (10, 18, 34) or shortcut_type != "B":
+            raise NotImplementedError("only the BasicBlock / shortcut-B variants used by the config are built")
         nblocks = {10: [1, 1, 1, 1], 18: [2, 2, 2, 2], 34: [3, 4, 6, 3]}[depth]
         planes = [int(c * widen_factor) for c in block_inplanes]
         self.in_planes = planes[0]
-        self.out_indices, self.num_stage, self.crp3d = out_indices, num_stage, False
+        self.out_indices, self.num_stage, self.crp3d = out_indices, num_stage, bool(crp3d)
         self.input_proj = nn.Sequential(Conv3d(n_input_channels, self.in_planes, 1, 1, 0, bias=False),
                                         build_norm_layer(norm_cfg, self.in_planes)[1], nn.ReLU(inplace=True))
         self.layers = nn.ModuleList()
         for i, c in enumerate(planes[:num_stage]):
             self.layers.append(self._make_layer(c, nblocks[i], block_strides[i], norm_cfg))
+        if self.crp3d:
+            if F.storage_bf16():
+                raise NotImplementedError("crp3d=True runs in fp32 only: the relation kernels have no bf16 storage form")
+            if not 0 <= crp_level < len(self.layers):
+                raise ValueError(f"crp_level {crp_level} names no built stage (num_stage={len(self.layers)})")
+            self.crp_level = crp_level
+            self.CP_mega_voxels = CPMegaVoxels(planes[crp_level], tuple(crp_size), bn_momentum=0.1)
+        self.forward_dic = {}
         fuse_relu_(self)
         for m in self.modules():
             if isinstance(m, Conv3d):
@@ -66,11 +78,24 @@ class CustomResNet3D(nn.Module):
         layers += [BasicBlock3d(planes, planes, norm_cfg=norm_cfg) for _ in range(1, blocks)]
         return nn.Sequential(*layers)
 
+    def crp_loss(self, CP_mega_matrices=None, CP_mega_labels=None):
+        """The relation loss of the last forward's ``P_logits`` (resnet3d.py:213-217).  ``CP_mega_labels``: the loader's
+        down-sampled label grid uint8 [B, X, Y, Z] (``CreateRelationLabels(relations=True)``), from which the fused kernel derives
+        the relation bits; ``CP_mega_matrices``: the reference's dense [B, 4, N, Mc] matrices, which take precedence and run the
+        tensor form.  A relation without a positive in the batch has pos_weight 1 (the reference returns NaN)."""
+        if not self.crp3d or "crp_logits" not in self.forward_dic:
+            raise RuntimeError("crp_loss needs crp3d=True and a forward pass")
+        return F.relation_loss(self.forward_dic["crp_logits"], CP_mega_labels, CP_mega_matrices)
+
     def forward(self, x):
         x = self.input_proj(x)
         res = []
         for i, layer in enumerate(self.layers):
             x = layer(x)
+            if self.crp3d and self.crp_level == i:
+                outputs = self.CP_mega_voxels(x)
+                self.forward_dic["crp_logits"] = outputs["P_logits"]
+                x = outputs["x"]
             if i in self.out_indices:
                 if i + 1 < len(self.layers):
                     x, out = F.fork(x)                       # next stage + neck

@@ -408,6 +408,93 @@ def frustum_case(name):
     return logits, ids, dists
 
 
+# Cases of the context-relation-prior tests (tools/make_golden_crp.py records the reference on them).
+# Down-sampling: name -> (label grid, downscale).  Hashed labels 0..19 and 255 with planted blocks (block index in the coarse
+# grid's flat order -> (value, count) pairs, the rest of the block stays hashed only where the counts do not fill it):
+#   D8 (threshold 486.4): 0 exactly 486 empty-or-255 voxels (a class wins), 1 exactly 487 with more zeros (0), 2 exactly 487 with
+#   more 255s (255), 3 a 0 / 255 tie (255), 4 classes 7 and 3 tie (3), 5 all 255, 6 all 0;
+#   D2 (threshold 7.6): 0 seven empty voxels and one of class 4 (4), 1 a 4 / 4 tie of 0 and 255 (255), 2 five zeros and three
+#   255s (0), 3 classes 9 and 2 tie with four voxels each (2), 4 all 255.
+CRP_DOWNSAMPLE_CASES = {"D8": ((32, 16, 16), 8), "D2": ((8, 6, 4), 2), "D4": ((32, 32, 8), 4)}
+CRP_DOWNSAMPLE_PLANTS = {
+    "D8": {0: ((0, 300), (255, 186), (11, 20), (6, 6)), 1: ((0, 300), (255, 187), (11, 25)), 2: ((0, 200), (255, 287), (11, 25)),
+           3: ((0, 250), (255, 250), (5, 12)), 4: ((7, 100), (3, 100), (0, 312)), 5: ((255, 512),), 6: ((0, 512),)},
+    "D2": {0: ((0, 4), (255, 3), (4, 1)), 1: ((0, 4), (255, 4)), 2: ((0, 5), (255, 3)), 3: ((9, 4), (2, 4)), 4: ((255, 8),)},
+    "D4": {}}
+
+
+def crp_downsample_case(name):
+    """(labels uint8 [X,Y,Z], downscale) of CRP_DOWNSAMPLE_CASES[name]."""
+    grid, ds = CRP_DOWNSAMPLE_CASES[name]
+    lab = hash_uniform(f"crp_{name}_lab", grid, 0.0, 20.0).long().clamp_(0, 19).to(torch.uint8)
+    lab[hash_uniform(f"crp_{name}_ign", grid, 0.0, 1.0) < 0.15] = 255
+    lab[hash_uniform(f"crp_{name}_empty", grid, 0.0, 1.0) < 0.5] = 0
+    Ys, Zs = grid[1] // ds, grid[2] // ds
+    for blk, plants in CRP_DOWNSAMPLE_PLANTS[name].items():
+        vals = torch.cat([torch.full((n,), v, dtype=torch.uint8) for v, n in plants])
+        assert vals.numel() == ds ** 3
+        perm = torch.argsort(hash_uniform(f"crp_{name}_perm{blk}", (ds ** 3,), 0.0, 1.0))
+        x, y, z = blk // (Ys * Zs), (blk // Zs) % Ys, blk % Zs
+        lab[x * ds:(x + 1) * ds, y * ds:(y + 1) * ds, z * ds:(z + 1) * ds] = vals[perm].view(ds, ds, ds)
+    return lab, ds
+
+
+# Relation loss: name -> (B, relation grid).  A: all four relations have positives; B: labels 0 and 5 only, relation 1 (two
+# different non-empty classes) has no positive (the reference returns NaN, here pos_weight 1); C: ~20 % of the voxels 255 (rows
+# without a positive, skipped children) and logits of +-90 planted on ~2 % of the elements; D: two samples, the second all empty
+# but one voxel, counts pooled over the batch; E: Mc = 288 > one 256-wide workgroup and 72 row chunks (only scalars recorded).
+CRP_LOSS_CASES = {"A": (1, (4, 4, 2)), "B": (1, (6, 4, 2)), "C": (1, (4, 4, 4)), "D": (2, (4, 4, 2)), "E": (1, (18, 16, 8))}
+
+
+def crp_loss_case(name):
+    """(P_logits fp32 [B,4,Mc,N] ~ N(0, 2^2), labels uint8 [B,X,Y,Z]: the down-sampled grid) of CRP_LOSS_CASES[name]."""
+    B, grid = CRP_LOSS_CASES[name]
+    N = grid[0] * grid[1] * grid[2]
+    classes = torch.tensor([0, 0, 0, 5, 9, 13] if name != "B" else [0, 0, 5, 5], dtype=torch.uint8)
+    u = hash_uniform(f"crp_loss_{name}_cls", (B,) + grid, 0.0, float(len(classes))).long().clamp_(0, len(classes) - 1)
+    lab = classes[u]
+    if name in "CE":
+        lab[hash_uniform(f"crp_loss_{name}_ign", (B,) + grid, 0.0, 1.0) < 0.2] = 255
+    if name == "D":
+        lab[1] = 0
+        lab[1, 2, 1, 1] = 9
+    P = hash_normal(f"crp_loss_{name}_x", (B, 4, N // 8, N), 2.0)
+    if name == "C":
+        big = hash_uniform("crp_loss_C_big", tuple(P.shape), 0.0, 1.0)
+        P = torch.where(big < 0.01, torch.full_like(P, 90.0), torch.where(big > 0.99, torch.full_like(P, -90.0), P))
+    return P, lab
+
+
+# Relation gather: name -> (B, R, N, Mc, C2, Cin).  The kernel's tiles are 128 rows x 128 columns x 16 along the reduction; the
+# three products put N, Mc and C2 on each of those axes in turn.  T: the module's own tiny shape, every size below one tile; U: Mc
+# = 3 and C2 = 10 (rows that are not 16-byte aligned), Cin = 2; V: two samples, two relations, no size a multiple of its tile; W:
+# every size spans several tiles, Cin = 6 puts the context slice off the 16-byte grid; X: the true depth Mc = 512 and N = 4096
+# (eight slices of the context gradient's reduction) with a small C2.
+CRP_GATHER_CASES = {"T": (1, 4, 32, 4, 16, 8), "U": (1, 2, 24, 3, 10, 2), "V": (2, 2, 200, 20, 36, 0), "W": (1, 4, 384, 144, 272, 6),
+                    "X": (1, 4, 4096, 512, 16, 0)}
+
+
+def crp_gather_case(name):
+    """(P_logits [B,R,Mc,N] ~ N(0, 2^2), context [B,Mc,C2], x [B,Cin,N] or None, upstream gradient [B,Cin + R C2,N]), fp32."""
+    B, R, N, Mc, C2, Cin = CRP_GATHER_CASES[name]
+    P = hash_normal(f"crp_gather_{name}_p", (B, R, Mc, N), 2.0)
+    ctx = hash_normal(f"crp_gather_{name}_c", (B, Mc, C2))
+    x = hash_normal(f"crp_gather_{name}_x", (B, Cin, N)) if Cin else None
+    g = hash_normal(f"crp_gather_{name}_g", (B, Cin + R * C2, N))
+    return P, ctx, x, g
+
+
+CRP_BLOCK = dict(feature=8, size=(4, 4, 2), batch=2)
+
+
+def crp_block_case():
+    """(input fp32 [2,8,4,4,2], weights of sum(x * wx) + sum(P_logits * wp): the scalar whose input gradient is recorded)."""
+    f, size, B = CRP_BLOCK["feature"], CRP_BLOCK["size"], CRP_BLOCK["batch"]
+    N = size[0] * size[1] * size[2]
+    return (hash_normal("crp_block_x", (B, f) + size), hash_normal("crp_block_wx", (B, f) + size),
+            hash_normal("crp_block_wp", (B, 4, N // 8, N)))
+
+
 def synthetic_sample(cfg, B=1, C_in=640, tag="s0", with_targets=True):
     """Image-neck outputs for both views + geometry + targets, all hash-generated.
 
