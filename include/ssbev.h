@@ -666,6 +666,33 @@ size_t ssbev_crp_gather_bwd_workspace(const ssbev_crp_gather_dims* d);
 int ssbev_crp_gather_bwd(const float* logits, const float* context, const float* grad_out, float* grad_logits, float* grad_context,
                          const ssbev_crp_gather_dims* d, void* ws, size_t ws_bytes, ssbev_stream_t stream);
 
+/* Lifted-point position encoder (since version 118): point_xyz_channel of the reference's voxel_pooling
+ * (ViewTransformerLSSVoxel.py:432-476) without a tensor that has a row per point.  A kept point p (vox[p] >= 0) at ego position
+ * g has the unit position u = ((g - lo) / (hi - lo) - 0.5) * 2, each step rounded to fp32 as the tensor expression rounds it.
+ *   geom      [B, P, 3] fp32;  vox [B P] int32;  starts / order / long_list: the tables of ssbev_pool_prepare2 for these points
+ *             (long_list may be NULL in _fwd: every list is then summed by the lanes of its voxel)
+ *   moments   [10] double (device): count, sum u (x, y, z), sum u u^T (xx, xy, xz, yy, yz, zz) over the kept points;
+ *             per-workgroup double sums folded in a fixed order: no atomics, every run gives the same bits
+ *   coef      [6, M] fp32 (device), per channel m: w_m / s_m (3 rows), (b1_m - mu_m) / s_m, gamma_m, beta_m, where
+ *             h = W1 u + b1 is the first Linear, mu / s the mean and standard deviation BatchNorm1d normalises with
+ *   _fwd      S [B, nx, ny, nz, M] fp32 (channels-last, 16-byte stores): S[v] = sum over the points of v, in ascending point
+ *             order and sequentially in fp32, of relu(gamma hhat + beta), hhat = fma(c0, ux, fma(c1, uy, fma(c2, uz, c3)));
+ *             zeros for empty voxels.  Lists of more than 32 points: 64 / (M / 4) strided slices folded in slice order
+ *   _bwd      sums [5, M] double (device): sum gz, sum gz hhat, sum gz ux, sum gz uy, sum gz uz over all kept points, with
+ *             gz = gS[v(p)] [z_p > 0] and z recomputed by the expression of _fwd (the masks agree bit for bit); gS is laid
+ *             out as S and read once per voxel.  Per-workgroup double sums over fixed voxel ranges, folded in workgroup order
+ * SSBEV_EINVAL before any device work: NULL pointers (d included), non-positive dims, M outside 4 .. 256 or no multiple of
+ * 4, hi <= lo or a non-finite bound, B P >= 2^31, B nx ny nz >= 2^31;  SSBEV_EWORKSPACE: ws_bytes below the query (one query
+ * serves _moments and _bwd), which answers 0 for refused dims. */
+typedef struct { int B, P, nx, ny, nz, M; float lo[3], hi[3]; } ssbev_point_xyz_dims;
+size_t ssbev_point_xyz_workspace(const ssbev_point_xyz_dims* d);
+int ssbev_point_xyz_moments(const float* geom, const int32_t* vox, double* moments, const ssbev_point_xyz_dims* d, void* ws,
+                            size_t ws_bytes, ssbev_stream_t stream);
+int ssbev_point_xyz_fwd(const float* geom, const int32_t* starts, const int32_t* order, const int32_t* long_list,
+                        const float* coef, float* S, const ssbev_point_xyz_dims* d, ssbev_stream_t stream);
+int ssbev_point_xyz_bwd(const float* geom, const int32_t* starts, const int32_t* order, const float* coef, const float* gS,
+                        double* sums, const ssbev_point_xyz_dims* d, void* ws, size_t ws_bytes, ssbev_stream_t stream);
+
 /* Running statistics of a training-mode BatchNorm from the (mean, rstd) ssbev_groupnorm_fwd returned with G == C over the
  * batch: running_mean <- (1-m) running_mean + m mean; running_var <- (1-m) running_var + m var n/(n-1)
  * (torch.nn.BatchNorm3d as built at ViewTransformerLSSVoxel.py:83-88; n = elements per channel). */

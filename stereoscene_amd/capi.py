@@ -117,6 +117,10 @@ class CrpGatherDims(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("B", "N", "Mc", "C2", "R")] + [("ld_out", C.c_int64)]
 
 
+class PointXyzDims(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("B", "P", "nx", "ny", "nz", "M")] + [("lo", C.c_float * 3), ("hi", C.c_float * 3)]
+
+
 class GemmDims(C.Structure):
     _fields_ = [("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("batch", C.c_int),
                 ("lda", C.c_int64), ("ldb", C.c_int64), ("ldc", C.c_int64), ("sa", C.c_int64), ("sb", C.c_int64), ("sc", C.c_int64),
@@ -351,7 +355,11 @@ SIGNATURES = {
     "ssbev_crp_gather_fwd": (C.c_int, [_P] * 3 + [C.POINTER(CrpGatherDims), _P]),
     "ssbev_crp_gather_bwd_workspace": (C.c_size_t, [C.POINTER(CrpGatherDims)]),
     "ssbev_crp_gather_bwd": (C.c_int, [_P] * 5 + [C.POINTER(CrpGatherDims), _P, C.c_size_t, _P]),
-    "ssbev_occ_dice_tail": (C.c_int, [_P, C.c_float, _P, _P, _P]),
+    "ssbev_point_xyz_workspace": (C.c_size_t, [C.POINTER(PointXyzDims)]),
+    "ssbev_point_xyz_moments": (C.c_int, [_P] * 3 + [C.POINTER(PointXyzDims), _P, C.c_size_t, _P]),
+    "ssbev_point_xyz_fwd": (C.c_int, [_P] * 6 + [C.POINTER(PointXyzDims), _P]),
+    "ssbev_point_xyz_bwd": (C.c_int, [_P] * 6 + [C.POINTER(PointXyzDims), _P, C.c_size_t, _P]),
+    "ssbev_occ_dice_tail":(C.c_int, [_P, C.c_float, _P, _P, _P]),
     "ssbev_lga_weights": (C.c_int, [_P, _P] + [C.c_int] * 4 + [_P]),
     "ssbev_occ_lga_workspace": (C.c_size_t, [C.POINTER(UpsampleDims)]),
     "ssbev_occ_lga_fwd": (C.c_int, [_P] * 4 + [C.c_float] * 2 + [_P] * 2 + [C.POINTER(UpsampleDims), _P, C.c_size_t, _P]),

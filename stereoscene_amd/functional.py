@@ -3043,7 +3043,226 @@ def imgseg_loss(seg_logits, seg_labels, class_weights, weight=1.0):
     return imgseg_loss_tensor(seg_logits, seg_labels, class_weights, weight)
 
 
-OCC_TAIL = os.environ.get("SSBEV_OCC_TAIL", "1") != "0"      # scalar loss algebra in one launch (0 = ~110 tiny ATen ops)
+# -------------------------------------------------------------------------------------------------
+# lifted-point position encoder (point_xyz_channel, VT:432-476; csrc/point_xyz.hip)
+# -------------------------------------------------------------------------------------------------
+POINT_XYZ = os.environ.get("SSBEV_POINT_XYZ", "1") != "0"    # fused position encoder (0 = the tensor form: one row per kept point)
+POINT_XYZ_MAX_WIDTH = 512                                    # Cxyz: M = Cxyz / 2 channels-last rows of at most 256 floats
+
+
+def voxel_index_tensor(geom, origin, dx, n):
+    """``voxel_index`` in ATen ops, on any device: geom [B, ..., 3] fp32, ``origin`` / ``dx`` / ``n`` = the host lists of
+    ``grid_host`` -> vox int32 [B*P] (linear voxel or -1), the same fp32 subtract, divide and truncation (VT:441-451)."""
+    B = geom.shape[0]
+    g = geom.reshape(B, -1, 3)
+    f = (g - torch.tensor(origin, dtype=g.dtype, device=g.device)) / torch.tensor(dx, dtype=g.dtype, device=g.device)
+    nn_ = torch.tensor([float(v) for v in n], dtype=g.dtype, device=g.device)
+    kept = ((f > -1.0) & (f < nn_)).all(-1)
+    i = torch.where(kept.unsqueeze(-1), f, torch.zeros_like(f)).long()
+    b = torch.arange(B, device=g.device).view(B, 1)
+    v = ((b * n[0] + i[..., 0]) * n[1] + i[..., 1]) * n[2] + i[..., 2]
+    return torch.where(kept, v, torch.full_like(v, -1)).to(torch.int32).reshape(-1)
+
+
+def point_xyz_unit(geom, pc_range):
+    """u = ((g - lo) / (hi - lo) - 0.5) * 2 for every point: geom [..., 3] -> [P, 3] in geom's dtype (VT:455-458)."""
+    g = geom.reshape(-1, 3)
+    lo = torch.tensor([float(v) for v in pc_range[:3]], dtype=g.dtype, device=g.device)
+    hi = torch.tensor([float(v) for v in pc_range[3:]], dtype=g.dtype, device=g.device)
+    return ((g - lo) / (hi - lo) - 0.5) * 2
+
+
+def point_xyz_pool_tensor(geom, vox, pc_range, grid, w1, b1, gamma, beta, w2, b2, running_mean=None, running_var=None,
+                          num_batches_tracked=None, training=True, eps=1e-5, momentum=0.1):
+    """The position encoder in its literal form, on any device: ``u[kept]`` is materialised, ``Linear(3, M) -> BatchNorm1d ->
+    ReLU -> Linear(M, Cxyz)`` runs on the [n_kept, .] matrices with plain torch ops (training mode: batch statistics over all
+    kept points of all samples, running statistics updated in place), the rows are summed per voxel (``bev_pool`` on the card,
+    ``index_add_`` on the CPU).  geom [B, ..., 3], vox int32 [B*P], ``grid`` = (nx, ny, nz) -> [B, Cxyz, nx, ny, nz].
+    Fewer than two kept points in training mode (the reference raises): zeros, zero gradients, statistics untouched."""
+    B = geom.shape[0]
+    nx, ny, nz = (int(v) for v in grid)
+    Cx = w2.shape[0]
+    kept = vox >= 0
+    u = point_xyz_unit(geom, pc_range)[kept]
+    n = u.shape[0]
+    if n == 0 or (training and n < 2):
+        zero = sum((p * 0).sum() for p in (w1, b1, gamma, beta, w2, b2))
+        return torch.zeros(B, Cx, nx, ny, nz, dtype=w2.dtype, device=geom.device) + zero
+    u = u.to(w1.dtype)
+    h = torch.nn.functional.linear(u, w1, b1)
+    h = torch.nn.functional.batch_norm(h, running_mean, running_var, gamma, beta, training, momentum, eps)
+    if training and num_batches_tracked is not None:
+        num_batches_tracked += 1
+    f = torch.nn.functional.linear(torch.relu(h), w2, b2)
+    idx = vox[kept].long()
+    if f.is_cuda and f.dtype == torch.float32:
+        iz, r = idx % nz, idx // nz
+        iy, r = r % ny, r // ny
+        ix, b = r % nx, r // nx
+        return bev_pool(f, torch.stack((ix, iy, iz, b), 1), B, nz, nx, ny).permute(0, 1, 3, 4, 2)
+    out = torch.zeros(B * nx * ny * nz, Cx, dtype=f.dtype, device=f.device).index_add_(0, idx, f)
+    return out.view(B, nx, ny, nz, Cx).permute(0, 4, 1, 2, 3)
+
+
+def point_xyz_moments_tensor(geom, vox, pc_range):
+    """[10] float64: count, sum u, sum u u^T (xx, xy, xz, yy, yz, zz) over the kept points, in ATen ops."""
+    u = point_xyz_unit(geom, pc_range)[vox >= 0].double()
+    x, y, z = u[:, 0], u[:, 1], u[:, 2]
+    cols = [torch.ones_like(x), x, y, z, x * x, x * y, x * z, y * y, y * z, z * z]
+    return torch.stack([c.sum() for c in cols])
+
+
+def point_xyz_stats(moments, w1, b1):
+    """Batch statistics of h = W1 u + b1 from the ten moments, float64 on the moments' device, nothing read back:
+    (n, ubar [3], cov [3, 3] biased, mu [M] = W1 ubar + b1, var [M] = w_m^T cov w_m)."""
+    m = moments.double()
+    n = m[0]
+    ns = torch.clamp(n, min=1.0)
+    ubar = m[1:4] / ns
+    s2 = torch.stack((m[4], m[5], m[6], m[5], m[7], m[8], m[6], m[8], m[9])).view(3, 3) / ns
+    cov = s2 - torch.outer(ubar, ubar)
+    w = w1.detach().double()
+    mu = w @ ubar + b1.detach().double()
+    var = torch.clamp(((w @ cov) * w).sum(1), min=0.0)
+    return n, ubar, cov, mu, var
+
+
+def _point_xyz_dims(B, P, grid, M, pc_range):
+    d = capi.PointXyzDims()
+    d.B, d.P, d.nx, d.ny, d.nz, d.M = int(B), int(P), int(grid[0]), int(grid[1]), int(grid[2]), int(M)
+    for i in range(3):
+        d.lo[i] = float(pc_range[i])
+        d.hi[i] = float(pc_range[3 + i])
+    return d
+
+
+def point_xyz_moments(geom, vox, pc_range, grid):
+    """The ten moments (``point_xyz_moments_tensor``) by ``ssbev_point_xyz_moments``: one pass over geom [B, ..., 3] + vox,
+    double sums folded in a fixed order, the result stays on the device.  They depend on the calibration only."""
+    if not (POINT_XYZ and geom.is_cuda):
+        return point_xyz_moments_tensor(geom, vox, pc_range)
+    lib = capi.load()
+    B = geom.shape[0]
+    g = _f32(geom, "point_xyz_moments").reshape(B, -1, 3).contiguous()
+    d = _point_xyz_dims(B, g.shape[1], grid, 4, pc_range)
+    out = torch.empty(10, dtype=torch.float64, device=g.device)
+    ws = _ws(lib.ssbev_point_xyz_workspace(C.byref(d)), g.device)
+    capi.check(lib.ssbev_point_xyz_moments(capi.ptr(g), capi.ptr(vox), capi.ptr(out), C.byref(d), capi.ptr(ws), ws.numel(),
+                                           capi.stream()), "ssbev_point_xyz_moments")
+    return out
+
+
+class _PointXyzSum(torch.autograd.Function):
+    """S[v] = sum_{p in v} relu(BN(W1 u_p + b1)) as [NV, M] (``ssbev_point_xyz_fwd / _bwd``): the per-point rows are never
+    formed.  Training mode normalises with the batch statistics that follow from the moments and updates the running
+    statistics on the device; eval mode with the running statistics.  Backward: five sums per channel from one walk, then
+
+        gbeta = sum gz,  ggamma = sum gz hhat,
+        gW1[m] = (gamma_m / s_m) (sum gz u - (gbeta_m / n) sum u - (ggamma_m / s_m) Cov(u) w_m),  gb1 = 0        (training)
+        gW1[m] = (gamma_m / s_m) sum gz u,  gb1 = (gamma_m / s_m) sum gz                                         (eval)."""
+
+    @staticmethod
+    def forward(ctx, w1, b1, gamma, beta, geom, starts, order, moments, running_mean, running_var, num_batches_tracked,
+                pc_range, grid, training, eps, momentum):
+        lib = capi.load()
+        B = geom.shape[0]
+        g = geom.detach().reshape(B, -1, 3).contiguous()
+        M = w1.shape[0]
+        d = _point_xyz_dims(B, g.shape[1], grid, M, pc_range)
+        n, ubar, cov, mu, var = point_xyz_stats(moments, w1, b1)
+        w64 = w1.detach().double()
+        if training:
+            valid = n >= 2.0
+            s = torch.sqrt(var + eps)
+            c3 = -(w64 @ ubar) / s
+            if running_mean is not None:
+                with torch.no_grad():
+                    unb = var * (n / torch.clamp(n - 1.0, min=1.0))
+                    running_mean.copy_(torch.where(valid, (1 - momentum) * running_mean.double() + momentum * mu,
+                                                   running_mean.double()))
+                    running_var.copy_(torch.where(valid, (1 - momentum) * running_var.double() + momentum * unb,
+                                                  running_var.double()))
+                    if num_batches_tracked is not None:
+                        num_batches_tracked += valid.to(num_batches_tracked.dtype)
+        else:
+            valid = torch.ones((), dtype=torch.bool, device=g.device)
+            s = torch.sqrt(running_var.detach().double() + eps)
+            c3 = (b1.detach().double() - running_mean.detach().double()) / s
+        coef = torch.cat(((w64 / s[:, None]).t(), c3[None], gamma.detach().double()[None], beta.detach().double()[None]), 0)
+        coef = (coef * valid).to(torch.float32).contiguous()                 # [6, M]; all zero without statistics: S = 0
+        nv = B * d.nx * d.ny * d.nz
+        S = torch.empty(nv, M, dtype=torch.float32, device=g.device)
+        nby = 4.0 * (4 * g.shape[0] * g.shape[1] + S.numel())
+        with _span("point_xyz", 2.0 * 4 * g.shape[0] * g.shape[1] * M, nby, f"fwd   point_xyz M={M} grid={d.nx}x{d.ny}x{d.nz}"):
+            capi.check(lib.ssbev_point_xyz_fwd(capi.ptr(g), capi.ptr(starts), capi.ptr(order), capi.ptr(getattr(order, "long_list", None)),
+                                               capi.ptr(coef), capi.ptr(S), C.byref(d), capi.stream()), "ssbev_point_xyz_fwd")
+        ctx.save_for_backward(g, starts, order.as_subclass(torch.Tensor), coef, w64, gamma.detach().double(), s, n, ubar, cov, moments, valid)
+        ctx.d, ctx.training = d, bool(training)
+        return S
+
+    @staticmethod
+    def backward(ctx, gS):
+        lib = capi.load()
+        g, starts, order, coef, w64, gam, s, n, ubar, cov, moments, valid = ctx.saved_tensors
+        d = ctx.d
+        M = d.M
+        gS = gS.contiguous()
+        sums = torch.empty(5, M, dtype=torch.float64, device=g.device)
+        ws = _ws(lib.ssbev_point_xyz_workspace(C.byref(d)), g.device)
+        with _span("point_xyz", 2.0 * 9 * g.shape[0] * g.shape[1] * M, 4.0 * (4 * g.shape[0] * g.shape[1] + gS.numel()),
+                   f"bwd   point_xyz M={M}"):
+            capi.check(lib.ssbev_point_xyz_bwd(capi.ptr(g), capi.ptr(starts), capi.ptr(order), capi.ptr(coef), capi.ptr(gS),
+                                               capi.ptr(sums), C.byref(d), capi.ptr(ws), ws.numel(), capi.stream()),
+                       "ssbev_point_xyz_bwd")
+        gbeta, ggamma, gzu = sums[0], sums[1], sums[2:5].t()                 # [M], [M], [M, 3]
+        k = (gam / s)[:, None]
+        if ctx.training:
+            ns = torch.clamp(n, min=1.0)
+            gw1 = k * (gzu - (gbeta / ns)[:, None] * moments[1:4][None] - (ggamma / s)[:, None] * (w64 @ cov))
+            gb1 = torch.zeros_like(gbeta)
+        else:
+            gw1 = k * gzu
+            gb1 = (gam / s) * gbeta
+        z = torch.zeros((), dtype=torch.float64, device=g.device)
+        gw1, gb1, ggamma, gbeta = (torch.where(valid, t, z).to(torch.float32) for t in (gw1, gb1, ggamma, gbeta))
+        return (gw1, gb1, ggamma, gbeta) + (None,) * 12
+
+
+def point_xyz_pool(geom, tables, pc_range, grid, w1, b1, gamma, beta, w2, b2, running_mean=None, running_var=None,
+                   num_batches_tracked=None, training=True, eps=1e-5, momentum=0.1, moments=None):
+    """``point_xyz_channel``: P[v] = sum_{p in v} Linear(relu(BN(Linear(u_p)))) = W2 S[v] + n_v b2 -> [B, Cxyz, nx, ny, nz]
+    (channels-last memory) for geom [B, ..., 3] and ``tables`` = lift_splat_tables of it.  fp32 CUDA tensors with ``POINT_XYZ``
+    on take the fused path: statistics from ``moments`` (``point_xyz_moments``; computed here when None), S by
+    ``_PointXyzSum``, the second Linear as a row-wise GEMM on the [NV, M] voxel sums (``small_linear``: forward, gS and gW2
+    on the own GEMM kernels), the bias term as one addcmul with the list lengths.  Anything else: ``point_xyz_pool_tensor``."""
+    vox, starts, order = tables
+    M, Cx = w1.shape[0], w2.shape[0]
+    fused = POINT_XYZ and geom.is_cuda and geom.dtype == torch.float32 and w1.dtype == torch.float32
+    if geom.is_cuda and storage_bf16():
+        raise NotImplementedError("point_xyz_channel is built for fp32 only (SSBEV_PRECISION=bf16 is refused)")
+    if not fused:
+        return point_xyz_pool_tensor(geom, vox, pc_range, grid, w1, b1, gamma, beta, w2, b2, running_mean, running_var,
+                                     num_batches_tracked, training, eps, momentum)
+    if M % 4 or not 4 <= M <= POINT_XYZ_MAX_WIDTH // 2 or Cx % 4:
+        raise capi.SsbevError(f"point_xyz_pool: M = {M} (a multiple of 4 up to {POINT_XYZ_MAX_WIDTH // 2}) and Cxyz = {Cx} refused")
+    if not training and (running_mean is None or running_var is None):
+        raise ValueError("point_xyz_pool: eval mode needs running statistics")
+    B = geom.shape[0]
+    nx, ny, nz = (int(v) for v in grid)
+    if moments is None:
+        with torch.no_grad():
+            moments = point_xyz_moments(geom, vox, pc_range, grid)
+    S = _PointXyzSum.apply(w1, b1, gamma, beta, geom, starts, order, moments, running_mean, running_var, num_batches_tracked,
+                           tuple(float(v) for v in pc_range), (nx, ny, nz), bool(training), float(eps), float(momentum))
+    with torch.no_grad():
+        cnt = (starts[1:] - starts[:-1]).to(torch.float32)
+        if training:
+            cnt = cnt * (moments[0] >= 2.0)
+    P = torch.addcmul(small_linear(S, w2), cnt[:, None], b2[None])
+    return from_cl(P.view(B, nx, ny, nz, Cx))
+
+
+OCC_TAIL =os.environ.get("SSBEV_OCC_TAIL", "1") != "0"      # scalar loss algebra in one launch (0 = ~110 tiny ATen ops)
 
 
 class _OccLossTail(torch.autograd.Function):

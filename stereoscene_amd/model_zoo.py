@@ -16,7 +16,7 @@ def image_branch_cfg(arch="b7"):
 
 def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False, loss_depth_type="bce", voxel_ohem=0.0,
               ohem_topk=0.25, frustum_dist=0.0, voxel_dice=0.0, voxel_lga=0.0, imgseg=False, loss_seg_weight=1.0,
-              lift_with_imgseg=False, imgseg_labels="img_seg", crp3d=False, crp_level=2):
+              lift_with_imgseg=False, imgseg_labels="img_seg", crp3d=False, crp_level=2, point_xyz_channel=0, point_xyz_mode="cat"):
     """Same structure and hyper-parameters as the reference config's ``model`` dict for the sizes in ``cfg`` (a
     synthetic.CFG_*).  ``image_branch=False`` (default, the benchmarked hot path a1-a16) leaves the 2-D
     image backbone/neck out: the detector then takes the image-neck features in place of raw images.  ``loss_depth_type``:
@@ -31,10 +31,16 @@ def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False, 
     right-view map, or "img_seg_left").  ``lift_with_imgseg=True`` lifts the 20 class probabilities with the features: the 3-D
     encoder then takes ``numC_Trans + 20`` channels.  ``crp3d=True`` builds the 3-D encoder's context relation prior behind stage
     ``crp_level`` (on that stage's grid: ``crp_size``) and adds ``loss_rel_ce``; the training call then needs ``CP_mega_labels``
-    (pipelines.CreateRelationLabels(relations=True)) or a dense ``CP_mega_matrix``."""
+    (pipelines.CreateRelationLabels(relations=True)) or a dense ``CP_mega_matrix``.  ``point_xyz_channel`` > 0 (a multiple of 8)
+    pools a learned encoding of every lifted point's position next to the features (``point_xyz_mode`` "cat": the 3-D encoder
+    takes that many more channels; "add": the width is ``numC_Trans`` and the encoding is added), fp32 only."""
     seg = dict(imgseg=True, imgseg_class=20, loss_seg_weight=float(loss_seg_weight), lift_with_imgseg=bool(lift_with_imgseg)) \
         if imgseg else {}
     bev_in = numC_Trans + (20 if imgseg and lift_with_imgseg else 0)
+    xyz = {}
+    if point_xyz_channel:
+        xyz = dict(point_xyz_channel=int(point_xyz_channel), point_xyz_mode=point_xyz_mode, point_cloud_range=list(cfg["pc_range"]))
+        bev_in += int(point_xyz_channel) if point_xyz_mode == "cat" else 0
     norm_cfg = dict(type="GN", num_groups=32, requires_grad=True)
     channels = [128, 256, 512]
     crp = {}
@@ -49,7 +55,7 @@ def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False, 
             type="ViewTransformerLiftSplatShootVoxel", downsample=cfg["downsample"], numC_input=640,
             cam_channels=30, semkitti=False, loss_depth_weight=1.0, grid_config=S.grid_config(cfg),
             data_config=dict(input_size=tuple(cfg["input_size"])), numC_Trans=numC_Trans, vp_megvii=False,
-            warp_align_corners=warp_align_corners, loss_depth_type=loss_depth_type, **seg),
+            warp_align_corners=warp_align_corners, loss_depth_type=loss_depth_type, **seg, **xyz),
         img_bev_encoder_backbone=dict(type="CustomResNet3D", depth=18, num_stage=3, n_input_channels=bev_in,
                                       block_inplanes=channels, out_indices=(0, 1, 2), norm_cfg=norm_cfg, **crp),
         img_bev_encoder_neck=dict(type="SECONDFPN3D", norm_cfg=norm_cfg, in_channels=channels,

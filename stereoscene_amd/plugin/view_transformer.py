@@ -513,10 +513,29 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
             raise ValueError(f"depth_kld_units must be one of {F.DEPTH_KLD_UNITS}, got {depth_kld_units!r}")
         self.depth_kld_units = depth_kld_units
         self.ablation = ablation
-        if point_xyz_channel or use_voxel_net or vp_megvii:
-            raise NotImplementedError("options unused by projects/configs/.../stereoscene.py are not built")
+        if use_voxel_net or vp_megvii:
+            raise NotImplementedError("use_voxel_net and vp_megvii (unused by projects/configs/.../stereoscene.py) are not built")
         if imgseg and imgseg_class != 20:
             raise ValueError(f"imgseg_class must be 20 (the SemanticKITTI class-weight table has 20 entries), got {imgseg_class}")
+        self.point_xyz_channel, self.point_xyz_mode = 0, point_xyz_mode
+        if point_xyz_channel:                         # lifted-point position encoder (VT:342-356)
+            if point_xyz_mode not in ("cat", "add"):
+                raise ValueError(f"point_xyz_mode must be 'cat' or 'add', got {point_xyz_mode!r}")
+            if point_xyz_mode == "add":
+                if imgseg and lift_with_imgseg:
+                    raise ValueError("point_xyz_mode='add' cannot be combined with lift_with_imgseg: the lifted features have "
+                                     f"{numC_Trans} + {imgseg_class} channels, the position encoding {numC_Trans}")
+                point_xyz_channel = numC_Trans        # VT:345
+            if point_xyz_channel < 0 or point_xyz_channel % 8 or point_xyz_channel > F.POINT_XYZ_MAX_WIDTH:
+                raise NotImplementedError(f"point_xyz_channel must be a multiple of 8 up to {F.POINT_XYZ_MAX_WIDTH} (its hidden width "
+                                          f"point_xyz_channel / 2 is stored in 16-byte channels-last rows), got {point_xyz_channel}")
+            if point_cloud_range is None or len(point_cloud_range) != 6:
+                raise ValueError("point_xyz_channel needs point_cloud_range = (x0, y0, z0, x1, y1, z1)")
+            self.point_xyz_channel = int(point_xyz_channel)
+            self.point_cloud_range = tuple(float(v) for v in point_cloud_range)
+            mid = self.point_xyz_channel // 2
+            self.point_xyz_encoder = nn.Sequential(nn.Linear(3, mid), nn.BatchNorm1d(mid), nn.ReLU(inplace=True),
+                                                   nn.Linear(mid, self.point_xyz_channel))
         self.grid_config, self.data_config = grid_config, data_config
         dx, bx, nx = gen_dx_bx(grid_config["xbound"], grid_config["ybound"], grid_config["zbound"])
         self.dx = nn.Parameter(dx, requires_grad=False)
@@ -609,12 +628,34 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
             c = getattr(self, "_geo_cache", None)
             if c is not None and c[2] is grid and len(c[0]) == len(calib) and \
                     all(a is b and a._version == v for a, (b, v) in zip(calib, c[0])):
+                self._xyz_geo = c[3]
                 return c[1]
         geom = self.get_geometry(*calib)
-        tables = F.lift_splat_tables(geom, self.bx, self.dx, self.nx, grid_host=grid)
+        xyz = None
+        if self.point_xyz_channel and not geom.is_cuda:      # the position encoder's tensor form needs the voxel ids only
+            tables = (F.voxel_index_tensor(geom, *grid), None, None)
+        else:
+            tables = F.lift_splat_tables(geom, self.bx, self.dx, self.nx, grid_host=grid)
+        if self.point_xyz_channel:
+            # the position encoder reads the points again (12 bytes each); its ten moments depend on the calibration only and
+            # are kept with the tables
+            with torch.no_grad():
+                xyz = (geom, F.point_xyz_moments(geom, tables[0], self.point_cloud_range, grid[2]))
+        self._xyz_geo = xyz
         if getattr(self, "geometry_cache", False):
-            self._geo_cache = ([(t, t._version) for t in calib], tables, grid)
+            self._geo_cache = ([(t, t._version) for t in calib], tables, grid, xyz)
         return tables
+
+    def point_xyz_pool(self, geom, tables, moments=None):
+        """Voxel sums of the position encoding of the lifted points (VT:453-463 + the pooling): [B, Cxyz, X, Y, Z]."""
+        if not self.point_xyz_channel:
+            raise RuntimeError("point_xyz_pool needs point_xyz_channel > 0")
+        lin1, bn, _, lin2 = self.point_xyz_encoder
+        if self.training and bn.momentum is None:
+            raise NotImplementedError("point_xyz_encoder: cumulative-average BatchNorm (momentum=None) is not built")
+        return F.point_xyz_pool(geom, tables, self.point_cloud_range, self._grid_host()[2], lin1.weight, lin1.bias, bn.weight, bn.bias,
+                                lin2.weight, lin2.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                                training=bn.training or bn.running_mean is None, eps=bn.eps, momentum=bn.momentum, moments=moments)
 
     def _side_stream(self, x):
         from .. import streams
@@ -659,13 +700,25 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
         """Reference-shaped entry (VT:432-476): x [B,N,D,H,W,C] materialised -> [B,C,X,Y,Z] via the
         bev_pool drop-in.  ``forward`` uses the fused functional.lift_splat instead."""
         B, N, D, H, W, C = x.shape
-        vox, idx3 = F.voxel_index(geom_feats, self.bx, self.dx, self.nx, return_idx=True)
-        kept = vox >= 0
-        bcol = torch.arange(B, device=x.device, dtype=torch.int32).repeat_interleave(N * D * H * W)[:, None]
-        coords = torch.cat((idx3, bcol), 1)[kept]
         n = [int(v) for v in self.nx.tolist()]
-        final = F.bev_pool(x.reshape(-1, C)[kept], coords, B, n[2], n[0], n[1])
-        return final.permute(0, 1, 3, 4, 2)
+        if self.point_xyz_channel and not x.is_cuda:          # the tensor form end to end (there is no CPU pooling kernel)
+            vox = F.voxel_index_tensor(geom_feats, *self._grid_host())
+            kept = vox >= 0
+            final = torch.zeros(B * n[0] * n[1] * n[2], C, dtype=x.dtype).index_add_(0, vox[kept].long(), x.reshape(-1, C)[kept])
+            final = final.view(B, n[0], n[1], n[2], C).permute(0, 4, 1, 2, 3)
+        else:
+            vox, idx3 = F.voxel_index(geom_feats, self.bx, self.dx, self.nx, return_idx=True)
+            kept = vox >= 0
+            bcol = torch.arange(B, device=x.device, dtype=torch.int32).repeat_interleave(N * D * H * W)[:, None]
+            coords = torch.cat((idx3, bcol), 1)[kept]
+            final = F.bev_pool(x.reshape(-1, C)[kept], coords, B, n[2], n[0], n[1]).permute(0, 1, 3, 4, 2)
+        if self.point_xyz_channel:                            # VT:453-463 in the tensor form: one encoder row per kept point
+            lin1, bn, _, lin2 = self.point_xyz_encoder
+            P = F.point_xyz_pool_tensor(geom_feats, vox, self.point_cloud_range, n, lin1.weight, lin1.bias, bn.weight, bn.bias,
+                                        lin2.weight, lin2.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                                        training=bn.training, eps=bn.eps, momentum=bn.momentum)
+            final = torch.cat((final, P), 1) if self.point_xyz_mode == "cat" else final + P
+        return final
 
     # losses -----------------------------------------------------------------------------------
     def get_downsampled_gt_depth(self, gt_depths):
@@ -766,4 +819,8 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
             seg_prob = F.softmax(self.forward_dic["imgseg_logits"].float().contiguous(), dim=1)
             img_feat = torch.cat((img_feat.float(), seg_prob), dim=1)
         bev_feat = F.lift_splat(depth_prob, img_feat, None, self.bx, self.dx, self.nx, grid_host=self._grid_host(), tables=tables)
+        if self.point_xyz_channel:                    # VT:453-463: the points' position encoding, pooled next to the features
+            geom, moments = self._xyz_geo
+            P = self.point_xyz_pool(geom, tables, moments)
+            bev_feat = torch.cat((bev_feat, P), dim=1) if self.point_xyz_mode == "cat" else bev_feat + P
         return bev_feat, depth_prob

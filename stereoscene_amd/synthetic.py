@@ -495,6 +495,69 @@ def crp_block_case():
             hash_normal("crp_block_wp", (B, 4, N // 8, N)))
 
 
+# Cases of the position-encoder tests (tools/make_golden_point_xyz.py records the reference on them), on CFG_T's frustum (D = 16,
+# 8 x 20 feature map: 2 560 points per sample): name -> (B, Cxyz, mode, training, pc_range or None = CFG_T's, occ_size or None).
+# E: a shrunk range with large voxels (most points outside, the rest crowded into a few voxels: lists of more than 32 and more
+# than 256 points next to empty voxels); F: eval mode with hashed running statistics; G: a range no point falls into.
+POINT_XYZ_CASES = {"A": (1, 16, "cat", True, None, None), "B": (2, 16, "add", True, None, None),
+                   "C": (1, 128, "cat", True, None, None), "D": (1, 8, "cat", True, None, None),
+                   "E": (1, 24, "cat", True, (0.0, -3.2, -2.0, 6.0, 3.2, 4.4), (4, 4, 4)),
+                   "F": (1, 16, "cat", False, None, None),
+                   "G": (1, 16, "cat", True, (100.0, 100.0, 100.0, 112.8, 112.8, 106.4), None)}
+POINT_XYZ_SEED = {n: 0 for n in POINT_XYZ_CASES}    # bumped when the generator refuses a case (a pre-activation or a point too close to a decision)
+POINT_XYZ_PARAMS = ("0.weight", "0.bias", "1.weight", "1.bias", "3.weight", "3.bias")
+
+
+def point_xyz_case(name):
+    """dict of a POINT_XYZ_CASES entry: cfg (CFG_T with the case's range / grid), B, Cxyz, mode, training, calib (the six tensors
+    of get_geometry; B: a yaw + translation in the second sample's 4x4 BEV matrix), geom fp32 [B,1,16,8,20,3] (the tensor form
+    of get_geometry on the CPU), grid_host = (origin, dx, n), state (the encoder's state dict, reference names), G fp32
+    [B,Cxyz,X,Y,Z]: the weights of the recorded scalar sum(P * G)."""
+    from types import SimpleNamespace
+    from .plugin.view_transformer import ViewTransformerLiftSplatShootVoxel as VT, gen_dx_bx
+    B, Cx, mode, training, rng, occ = POINT_XYZ_CASES[name]
+    cfg = dict(CFG_T, pc_range=rng or CFG_T["pc_range"], occ_size=occ or CFG_T["occ_size"])
+    tag = f"point_xyz/{name}/{POINT_XYZ_SEED[name]}"
+    grid = grid_config(cfg)
+    view = frustum_view(cfg, B=B, bda=torch.eye(4) if name == "B" else None)
+    calib = [t.clone() for t in view[1:]]
+    if name == "B":
+        a = 0.2
+        calib[5][1] = torch.tensor([[math.cos(a), -math.sin(a), 0.0, 0.3], [math.sin(a), math.cos(a), 0.0, -0.2],
+                                    [0.0, 0.0, 1.0, 0.1], [0.0, 0.0, 0.0, 1.0]])
+    ns = SimpleNamespace(data_config=dict(input_size=tuple(cfg["input_size"])), grid_config=grid, downsample=cfg["downsample"],
+                         _apply3x3=VT._apply3x3)
+    ns.frustum = VT.create_frustum(ns)
+    geom = VT.get_geometry(ns, *calib)
+    dx, bx, nx = gen_dx_bx(grid["xbound"], grid["ybound"], grid["zbound"])
+    grid_host = ((bx - dx / 2.0).tolist(), dx.tolist(), [int(v) for v in nx.tolist()])
+    M = Cx // 2
+    state = {"0.weight": hash_uniform(f"{tag}/w1", (M, 3), -1.0, 1.0), "0.bias": hash_uniform(f"{tag}/b1", (M,), -0.5, 0.5),
+             "1.weight": hash_uniform(f"{tag}/gamma", (M,), 0.5, 1.5), "1.bias": hash_uniform(f"{tag}/beta", (M,), -0.5, 0.5),
+             "1.running_mean": hash_uniform(f"{tag}/rm", (M,), -0.3, 0.3) if not training else torch.zeros(M),
+             "1.running_var": hash_uniform(f"{tag}/rv", (M,), 0.2, 0.8) if not training else torch.ones(M),
+             "1.num_batches_tracked": torch.tensor(0 if training else 7),
+             "3.weight": hash_uniform(f"{tag}/w2", (Cx, M), -0.3, 0.3), "3.bias": hash_uniform(f"{tag}/b2", (Cx,), -0.1, 0.1)}
+    # The ReLU's kink must not sit on a point: with thousands of points per channel a hashed beta puts some pre-activation within
+    # rounding of 0, and the fp32 evaluations would disagree on its mask.  beta_m is therefore moved (in float64, from the inputs
+    # alone) to the middle of the widest gap between consecutive sorted values of gamma_m hhat_m whose middle is within half of the
+    # channel's largest magnitude -- the normalised values themselves do not depend on beta.
+    from . import functional as F
+    kept = F.voxel_index_tensor(geom, *grid_host) >= 0
+    if int(kept.sum()) >= 2:
+        r = torch.tensor(cfg["pc_range"], dtype=torch.float32).double()
+        u = ((geom.reshape(-1, 3)[kept].double() - r[:3]) / (r[3:] - r[:3]) - 0.5) * 2
+        h = u @ state["0.weight"].double().t() + state["0.bias"].double()
+        mu, var = (h.mean(0), h.var(0, unbiased=False)) if training else (state["1.running_mean"].double(), state["1.running_var"].double())
+        y = (state["1.weight"].double() * (h - mu) / torch.sqrt(var + 1e-5)).sort(0).values          # [n_kept, M]
+        mid, gap = (y[1:] + y[:-1]) / 2, y[1:] - y[:-1]
+        gap = torch.where(mid.abs() <= 0.5 * y.abs().max(0).values, gap, torch.zeros_like(gap))
+        state["1.bias"] = (-mid.gather(0, gap.argmax(0, keepdim=True))[0]).float()
+    n = grid_host[2]
+    return dict(cfg=cfg, B=B, Cxyz=Cx, mode=mode, training=training, calib=calib, geom=geom, grid_host=grid_host, state=state,
+                G=hash_uniform(f"{tag}/G", (B, Cx, n[0], n[1], n[2]), -1.0, 1.0))
+
+
 def synthetic_sample(cfg, B=1, C_in=640, tag="s0", with_targets=True):
     """Image-neck outputs for both views + geometry + targets, all hash-generated.
 
