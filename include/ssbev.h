@@ -693,6 +693,40 @@ int ssbev_point_xyz_fwd(const float* geom, const int32_t* starts, const int32_t*
 int ssbev_point_xyz_bwd(const float* geom, const int32_t* starts, const int32_t* order, const float* coef, const float* gS,
                         double* sums, const ssbev_point_xyz_dims* d, void* ws, size_t ws_bytes, ssbev_stream_t stream);
 
+/* Point-level branch of the occupancy head (since version 119; occhead.py:171-236 sample_point_feats + feature_sampling): every
+ * point of the batch samples the voxel feature maps trilinearly and the image features bilinearly, as F.grid_sample with zero
+ * padding and align_corners=False does (source index ((g + 1) S - 1) / 2 in fp32, ATen's corner weights and corner order;
+ * corners outside the map are skipped, never clamped).  csrc/point_head.hip.
+ *   points    [N, 3] fp32: the normalised coordinates g of all samples' points, sample after sample
+ *   offsets   [B + 1] int32 (device): first point of every sample, offsets[B] = N
+ *   f0 .. f3  the L <= 4 levels, channels-last [B, X_l, Y_l, Z_l, C] fp32 (the unused ones NULL)
+ *   axis_xyz  0: g = (x, y, z) is handed to the sampler as the reference hands it, so that x walks the Z axis and z the X axis;
+ *             1: x walks X, y walks Y, z walks Z
+ *   rows      per_level = 1: [L, N, C];  per_level = 0: [N, C], the levels added in level order
+ *   ws        kept for _bwd: int32 keys | fp32 weights, one pair per (level, point, corner) in that order; a key is the cell
+ *             of the concatenated level grids the corner read, -1 for a skipped corner.  The keys sit at the start of ws
+ *   _bwd      starts / order: the CSR table ssbev_pool_prepare2 makes of the keys with dims (1, sum_l B X_l Y_l Z_l, 1, 1);
+ *             g0 .. g3 laid out as f0 .. f3: every cell = sum of weight * grad_rows over its list in list order, zeros for an
+ *             empty list.  Every element is written exactly once: no float atomics, the same bits on every run
+ * The image form: img [B, cams, H, W, C], uv [N, cams, 3] = (u, v, depth); a pair contributes when depth > 1e-5 and u, v lie
+ * strictly inside (-1, 1); rows [N, C] = sum over the cameras; keys over B cams H W pixels, 4 per (point, camera).  Masked
+ * pairs are never read (NaN features behind them are not scrubbed).
+ * SSBEV_EINVAL before any device work: NULL pointers (d included), non-positive dims, C no multiple of 4, L > 4, flags other
+ * than 0 / 1, 2^31 or more keys or cells;  SSBEV_EWORKSPACE: ws_bytes below the query, which answers 0 for refused dims. */
+typedef struct { int B, N, C, L; int X[4], Y[4], Z[4]; int axis_xyz, per_level; } ssbev_point_head_dims;
+typedef struct { int B, N, cams, C, H, W; } ssbev_point_img_dims;
+size_t ssbev_point_sample_workspace(const ssbev_point_head_dims* d);
+int ssbev_point_sample_fwd(const float* points, const int32_t* offsets, const float* f0, const float* f1, const float* f2,
+                           const float* f3, float* rows, const ssbev_point_head_dims* d, void* ws, size_t ws_bytes,
+                           ssbev_stream_t stream);
+int ssbev_point_sample_bwd(const float* grad_rows, const int32_t* starts, const int32_t* order, const void* ws, float* g0,
+                           float* g1, float* g2, float* g3, const ssbev_point_head_dims* d, ssbev_stream_t stream);
+size_t ssbev_point_img_workspace(const ssbev_point_img_dims* d);
+int ssbev_point_img_fwd(const float* img, const float* uv, const int32_t* offsets, float* rows, const ssbev_point_img_dims* d,
+                        void* ws, size_t ws_bytes, ssbev_stream_t stream);
+int ssbev_point_img_bwd(const float* grad_rows, const int32_t* starts, const int32_t* order, const void* ws, float* grad_img,
+                        const ssbev_point_img_dims* d, ssbev_stream_t stream);
+
 /* Running statistics of a training-mode BatchNorm from the (mean, rstd) ssbev_groupnorm_fwd returned with G == C over the
  * batch: running_mean <- (1-m) running_mean + m mean; running_var <- (1-m) running_var + m var n/(n-1)
  * (torch.nn.BatchNorm3d as built at ViewTransformerLSSVoxel.py:83-88; n = elements per channel). */

@@ -121,6 +121,15 @@ class PointXyzDims(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("B", "P", "nx", "ny", "nz", "M")] + [("lo", C.c_float * 3), ("hi", C.c_float * 3)]
 
 
+class PointHeadDims(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("B", "N", "C", "L")] + [(n, C.c_int * 4) for n in ("X", "Y", "Z")] + \
+        [("axis_xyz", C.c_int), ("per_level", C.c_int)]
+
+
+class PointImgDims(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("B", "N", "cams", "C", "H", "W")]
+
+
 class GemmDims(C.Structure):
     _fields_ = [("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("batch", C.c_int),
                 ("lda", C.c_int64), ("ldb", C.c_int64), ("ldc", C.c_int64), ("sa", C.c_int64), ("sb", C.c_int64), ("sc", C.c_int64),
@@ -359,6 +368,12 @@ SIGNATURES = {
     "ssbev_point_xyz_moments": (C.c_int, [_P] * 3 + [C.POINTER(PointXyzDims), _P, C.c_size_t, _P]),
     "ssbev_point_xyz_fwd": (C.c_int, [_P] * 6 + [C.POINTER(PointXyzDims), _P]),
     "ssbev_point_xyz_bwd": (C.c_int, [_P] * 6 + [C.POINTER(PointXyzDims), _P, C.c_size_t, _P]),
+    "ssbev_point_sample_workspace": (C.c_size_t, [C.POINTER(PointHeadDims)]),
+    "ssbev_point_sample_fwd": (C.c_int, [_P] * 7 + [C.POINTER(PointHeadDims), _P, C.c_size_t, _P]),
+    "ssbev_point_sample_bwd": (C.c_int, [_P] * 8 + [C.POINTER(PointHeadDims), _P]),
+    "ssbev_point_img_workspace": (C.c_size_t, [C.POINTER(PointImgDims)]),
+    "ssbev_point_img_fwd": (C.c_int, [_P] * 4 + [C.POINTER(PointImgDims), _P, C.c_size_t, _P]),
+    "ssbev_point_img_bwd": (C.c_int, [_P] * 5 + [C.POINTER(PointImgDims), _P]),
     "ssbev_occ_dice_tail":(C.c_int, [_P, C.c_float, _P, _P, _P]),
     "ssbev_lga_weights": (C.c_int, [_P, _P] + [C.c_int] * 4 + [_P]),
     "ssbev_occ_lga_workspace": (C.c_size_t, [C.POINTER(UpsampleDims)]),

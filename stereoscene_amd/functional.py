@@ -3262,7 +3262,250 @@ def point_xyz_pool(geom, tables, pc_range, grid, w1, b1, gamma, beta, w2, b2, ru
     return from_cl(P.view(B, nx, ny, nz, Cx))
 
 
-OCC_TAIL =os.environ.get("SSBEV_OCC_TAIL", "1") != "0"      # scalar loss algebra in one launch (0 = ~110 tiny ATen ops)
+# -------------------------------------------------------------------------------------------------
+# point-level branch of the head (occhead.py:171-236, 363-398; csrc/point_head.hip)
+# -------------------------------------------------------------------------------------------------
+POINT_HEAD = os.environ.get("SSBEV_POINT_HEAD", "1") != "0"  # fused point sampling and point CE (0 = the tensor forms: grid_sample, cross_entropy)
+POINT_AXIS_ORDERS = ("reference", "xyz")
+POINT_HEAD_MAX_LEVELS = 4
+
+
+def point_unit(points, pc_range):
+    """g = ((p[:, :3] - lo) / (hi - lo)) * 2 - 1 in the points' dtype, each step rounded as the tensor expression of
+    occhead.py:178-183 rounds it: [n, >= 3] -> [n, 3]."""
+    p = points[:, :3]
+    dt = np.float64 if p.dtype == torch.float64 else np.float32
+    lo = np.asarray(pc_range[:3], dtype=dt)
+    rng = np.asarray(pc_range[3:], dtype=dt) - lo                 # rounded in the points' dtype, as the tensor subtraction is
+    # the six bounds ride as scalar kernel arguments: no host tensor is copied to the device
+    return torch.stack([(p[:, i] - float(lo[i])) / float(rng[i]) for i in range(3)], 1) * 2 - 1
+
+
+def _point_offsets(counts, device):
+    """int32 [B + 1] on ``device`` from the host-known sample sizes: pinned staging + an asynchronous copy, nothing read back."""
+    offs = torch.tensor([0] + list(np.cumsum(counts)), dtype=torch.int32)
+    return offs.pin_memory().to(device, non_blocking=True) if torch.device(device).type == "cuda" else offs
+
+
+def point_sample_tensor(feats, g, counts, axis_order="reference", per_level=False):
+    """``point_sample`` as literal ``grid_sample`` calls, one per sample and level, on any device and in the features' dtype.
+
+    The reference hands g = (x, y, z) to ``grid_sample`` unflipped (occhead.py:186-189), and ``grid_sample``'s first grid
+    coordinate addresses the LAST tensor axis.  Seen on the CPU (and asserted by tests/test_point_head.py): on a [1, 1, 2, 3, 5]
+    map filled with 100 x + 10 y + z, the centre of cell (x, y, z) = (1, 1, 0), g = (0.5, 0, -0.8), reads 9.275 as given -- its
+    x = 0.5 walks the 5-long Z axis to index 3.25, its z = -0.8 the 2-long X axis to index -0.3, so 0.7 * (10 + 3.25) -- and
+    110, the cell's value, when given as (z, y, x).  ``axis_order="xyz"`` therefore flips the coordinates before the call."""
+    if axis_order not in POINT_AXIS_ORDERS:
+        raise ValueError(f"axis_order must be one of {POINT_AXIS_ORDERS}, got {axis_order!r}")
+    C_ = feats[0].shape[1]
+    g = g.to(feats[0].dtype)
+    if axis_order == "xyz":
+        g = g.flip(-1)
+    levels = []
+    for f in feats:
+        rows, at = [], 0
+        for b, n in enumerate(counts):
+            if n:
+                s = torch.nn.functional.grid_sample(f[b:b + 1], g[at:at + n].view(1, 1, 1, n, 3), mode="bilinear",
+                                                    padding_mode="zeros", align_corners=False)
+                rows.append(s.reshape(C_, n).t())
+            at += n
+        levels.append(torch.cat(rows, 0) if rows else f.new_zeros(0, C_))
+    return torch.stack(levels, 0) if per_level else sum(levels[1:], levels[0])
+
+
+def point_img_mask(uv):
+    """feature_sampling's mask (occhead.py:436-440): depth > 1e-5 and u, v strictly inside (-1, 1); uv [n, cams, 3] -> bool."""
+    return (uv[..., 2] > 1e-5) & (uv[..., 0] > -1.0) & (uv[..., 0] < 1.0) & (uv[..., 1] > -1.0) & (uv[..., 1] < 1.0)
+
+
+def point_img_sample_tensor(img_feats, uv, counts):
+    """``point_img_sample`` as literal ``grid_sample`` calls (occhead.py:196-206, 428-453): bilinear samples per camera,
+    ``nan_to_num``, times the mask, summed over the cameras."""
+    C_ = img_feats.shape[2]
+    uv = uv.to(img_feats.dtype)
+    rows, at = [], 0
+    for b, n in enumerate(counts):
+        if n:
+            p = uv[at:at + n]
+            s = torch.nn.functional.grid_sample(img_feats[b], p[..., :2].permute(1, 0, 2).unsqueeze(2), mode="bilinear",
+                                                padding_mode="zeros", align_corners=False)
+            s = torch.nan_to_num(s.squeeze(-1).permute(2, 0, 1))                     # [n, cams, C]
+            rows.append((s * point_img_mask(p).to(s.dtype).unsqueeze(-1)).sum(1))
+        at += n
+    return torch.cat(rows, 0) if rows else img_feats.new_zeros(0, C_)
+
+
+def _point_csr(ws, nk, cells):
+    """(starts, order) of the keys at the start of a sampling workspace: ``pool_prepare``'s stable sort, which drops the -1 keys
+    of skipped corners.  Its long-list output is not used: the gradient kernel walks every list in list order."""
+    starts, order = pool_prepare(ws[:4 * nk].view(torch.int32), 1, cells, 1, 1)
+    return starts, order.as_subclass(torch.Tensor)
+
+
+class _PointSample(torch.autograd.Function):
+    """``ssbev_point_sample_fwd / _bwd``: g [N, 3], offsets int32 [B + 1], levels [B, C, X, Y, Z] -> rows [L, N, C] or [N, C].
+    Forward keeps the (key, weight) pairs and, when a level needs a gradient, the CSR table of the keys; backward writes every
+    cell of every level once."""
+
+    @staticmethod
+    def forward(ctx, g, offs, axis_xyz, per_level, *feats):
+        lib = capi.load()
+        xcl = [to_cl(_f32(f, "point_sample")) for f in feats]
+        B, C_ = xcl[0].shape[0], xcl[0].shape[-1]
+        N = g.shape[0]
+        d = capi.PointHeadDims()
+        d.B, d.N, d.C, d.L, d.axis_xyz, d.per_level = B, N, C_, len(xcl), int(axis_xyz), int(per_level)
+        cells = 0
+        for l, x in enumerate(xcl):
+            d.X[l], d.Y[l], d.Z[l] = (int(v) for v in x.shape[1:4])
+            cells += x.numel() // C_
+        nws = lib.ssbev_point_sample_workspace(C.byref(d))
+        if not nws:
+            raise capi.SsbevError(f"point_sample: dims refused (N = {N}, C = {C_}, levels {[tuple(x.shape) for x in xcl]})")
+        ws = torch.empty(nws, dtype=torch.uint8, device=g.device)                   # kept for backward
+        rows = torch.empty((len(xcl), N, C_) if per_level else (N, C_), dtype=torch.float32, device=g.device)
+        ptrs = [capi.ptr(x) for x in xcl] + [None] * (POINT_HEAD_MAX_LEVELS - len(xcl))
+        with _span("point_head", 2.0 * 8 * len(xcl) * N * C_, 4.0 * 9 * len(xcl) * N * C_, f"fwd   point_sample N={N} C={C_}"):
+            capi.check(lib.ssbev_point_sample_fwd(capi.ptr(g), capi.ptr(offs), *ptrs, capi.ptr(rows), C.byref(d), capi.ptr(ws),
+                                                  ws.numel(), capi.stream()), "ssbev_point_sample_fwd")
+        if any(ctx.needs_input_grad[4:]):
+            starts, order = _point_csr(ws, len(xcl) * 8 * N, cells)
+            ctx.save_for_backward(starts, order, ws)
+        ctx.d, ctx.shapes = d, [x.shape for x in xcl]
+        return rows
+
+    @staticmethod
+    def backward(ctx, grows):
+        lib = capi.load()
+        starts, order, ws = ctx.saved_tensors
+        d = ctx.d
+        grows = grows.contiguous()
+        gf = [torch.empty(s, dtype=torch.float32, device=grows.device) for s in ctx.shapes]
+        ptrs = [capi.ptr(x) for x in gf] + [None] * (POINT_HEAD_MAX_LEVELS - len(gf))
+        with _span("point_head", 2.0 * 8 * d.L * d.N * d.C, 4.0 * sum(x.numel() for x in gf), f"bwd   point_sample N={d.N} C={d.C}"):
+            capi.check(lib.ssbev_point_sample_bwd(capi.ptr(grows), capi.ptr(starts), capi.ptr(order), capi.ptr(ws), *ptrs,
+                                                  C.byref(d), capi.stream()), "ssbev_point_sample_bwd")
+        return (None, None, None, None) + tuple(from_cl(x) for x in gf)
+
+
+class _PointImgSample(torch.autograd.Function):
+    """``ssbev_point_img_fwd / _bwd``: img [B, cams, C, H, W], uv [N, cams, 3], offsets -> rows [N, C].  The CSR table and the
+    gradient exist only when the image features require a gradient."""
+
+    @staticmethod
+    def forward(ctx, img, uv, offs):
+        lib = capi.load()
+        B, cams, C_, H, W = img.shape
+        icl = to_cl(_f32(img, "point_img_sample").reshape(B * cams, C_, H, W))        # [B cams, H, W, C]
+        N = uv.shape[0]
+        d = capi.PointImgDims(B, N, cams, C_, H, W)
+        nws = lib.ssbev_point_img_workspace(C.byref(d))
+        if not nws:
+            raise capi.SsbevError(f"point_img_sample: dims refused (N = {N}, img {tuple(img.shape)})")
+        ws = torch.empty(nws, dtype=torch.uint8, device=img.device)
+        rows = torch.empty(N, C_, dtype=torch.float32, device=img.device)
+        with _span("point_head", 2.0 * 4 * cams * N * C_, 4.0 * 5 * cams * N * C_, f"fwd   point_img N={N} C={C_}"):
+            capi.check(lib.ssbev_point_img_fwd(capi.ptr(icl), capi.ptr(uv), capi.ptr(offs), capi.ptr(rows), C.byref(d),
+                                               capi.ptr(ws), ws.numel(), capi.stream()), "ssbev_point_img_fwd")
+        if ctx.needs_input_grad[0]:
+            starts, order = _point_csr(ws, 4 * cams * N, B * cams * H * W)
+            ctx.save_for_backward(starts, order, ws)
+        ctx.d = d
+        return rows
+
+    @staticmethod
+    def backward(ctx, grows):
+        lib = capi.load()
+        starts, order, ws = ctx.saved_tensors
+        d = ctx.d
+        grows = grows.contiguous()
+        gi = torch.empty(d.B * d.cams, d.H, d.W, d.C, dtype=torch.float32, device=grows.device)
+        with _span("point_head", 2.0 * 4 * d.cams * d.N * d.C, 4.0 * gi.numel(), f"bwd   point_img N={d.N} C={d.C}"):
+            capi.check(lib.ssbev_point_img_bwd(capi.ptr(grows), capi.ptr(starts), capi.ptr(order), capi.ptr(ws), capi.ptr(gi),
+                                               C.byref(d), capi.stream()), "ssbev_point_img_bwd")
+        return from_cl(gi).reshape(d.B, d.cams, d.C, d.H, d.W), None, None
+
+
+def _point_head_fused(*ts):
+    if any(t.is_cuda for t in ts) and storage_bf16():
+        raise NotImplementedError("the head's point-level branch is built for fp32 only (SSBEV_PRECISION=bf16 is refused)")
+    return POINT_HEAD and all(t.is_cuda and t.dtype == torch.float32 for t in ts)
+
+
+def point_sample(feats, g, counts, axis_order="reference", per_level=False):
+    """Trilinear samples of the voxel feature maps at the points of a batch (occhead.py:185-189): ``feats`` = list of L levels
+    [B, C, X_l, Y_l, Z_l], g [N, 3] = ``point_unit`` of all samples' points one after the other, ``counts`` = the host list of
+    the B sample sizes -> [L, N, C] (``per_level``) or the sum over the levels [N, C].  fp32 CUDA tensors with ``POINT_HEAD`` on,
+    up to 4 levels of one width C % 4 == 0 and N > 0 take the fused path (one launch forward, one backward over a CSR table of the
+    corners: no float atomics); anything else ``point_sample_tensor``.  bf16 storage is refused."""
+    if axis_order not in POINT_AXIS_ORDERS:
+        raise ValueError(f"axis_order must be one of {POINT_AXIS_ORDERS}, got {axis_order!r}")
+    feats = list(feats)
+    if sum(counts) != g.shape[0] or any(f.shape[0] != len(counts) for f in feats):
+        raise ValueError("point_sample: counts must name every sample's points")
+    C_ = feats[0].shape[1]
+    ok = (_point_head_fused(g, *feats) and g.shape[0] > 0 and C_ % 4 == 0 and len(feats) <= POINT_HEAD_MAX_LEVELS
+          and all(f.dim() == 5 and f.shape[1] == C_ for f in feats))
+    if not ok:
+        return point_sample_tensor(feats, g, counts, axis_order, per_level)
+    offs = _point_offsets(counts, g.device)
+    return _PointSample.apply(g.detach().contiguous(), offs, axis_order == "xyz", bool(per_level), *feats)
+
+
+def point_img_sample(img_feats, uv, counts):
+    """Masked bilinear samples of the image features at the points' projections, summed over the cameras (occhead.py:196-206,
+    428-453): img_feats [B, cams, C, H, W], uv [N, cams, 3] = (u, v, depth) -> [N, C].  The fused path (fp32 CUDA, ``POINT_HEAD``
+    on, C % 4 == 0, N > 0) never reads a masked pair, so NaN features behind one are not scrubbed (the tensor form's
+    ``nan_to_num`` turns NaN samples of kept pairs into 0 as the reference does); the gradient wrt the image features is built
+    only when they require one."""
+    if sum(counts) != uv.shape[0] or img_feats.shape[0] != len(counts) or uv.shape[1] != img_feats.shape[1]:
+        raise ValueError(f"point_img_sample: img_feats {tuple(img_feats.shape)} and uv {tuple(uv.shape)} disagree")
+    if not (_point_head_fused(img_feats, uv) and uv.shape[0] > 0 and img_feats.shape[2] % 4 == 0):
+        return point_img_sample_tensor(img_feats, uv, counts)
+    return _PointImgSample.apply(img_feats, uv.detach().contiguous(), _point_offsets(counts, uv.device))
+
+
+def point_ce_loss_tensor(logits, labels):
+    """Unweighted ``CrossEntropyLoss(ignore_index=0)`` of logits [N, K] against labels [N] in ATen ops, as sum over count, so that
+    no labelled point gives 0 with a zero gradient (the reference: NaN).  Labels outside [1, K) are ignored."""
+    lab = _imgseg_labels(labels, logits.shape[1])
+    num = torch.nn.functional.cross_entropy(logits, lab, ignore_index=0, reduction="sum")
+    den = (lab > 0).sum().to(logits.dtype)
+    return num / torch.where(den > 0, den, torch.ones_like(den))
+
+
+def point_ce_loss(logits, labels):
+    """``loss_point_ce_`` before its weight (occhead.py:384-386).  On the fused path the [N, K] logits are the [1, K, N, 1] map of
+    the image-view segmentation kernel with unit class weights (``ssbev_imgseg_ce_fwd``: one wave per point, log-softmax, pick,
+    the partial sums folded in a fixed order by the shared ``block_fold256``): one deterministic pass, nothing read back."""
+    N, K = logits.shape
+    if (_point_head_fused(logits) and IMGSEG and labels.is_cuda and 2 <= K <= IMGSEG_MAX_CLASSES and 0 < N < 2 ** 24):
+        lab = labels.to(torch.float32).reshape(1, N, 1).contiguous()
+        cw = torch.ones(K, dtype=torch.float32, device=logits.device)
+        return _ImgSegCe.apply(logits.t().contiguous().view(1, K, N, 1), lab, cw, 1.0)
+    if N == 0:
+        return logits.sum() * 0.0
+    return point_ce_loss_tensor(logits, labels)
+
+
+def point_lovasz_loss(logits, labels):
+    """``loss_point_lovasz_`` before its weight (occhead.py:389-394): ``lovasz_softmax(softmax(logits), labels, ignore=0)`` on
+    the [1, K, N, 1, 1] view.  fp32 CUDA logits of 20 classes run on the fused Lovasz kernels (``lovasz_softmax``; the view is
+    already channels-last, so nothing is copied); anything else on ``losses.lovasz_softmax_tensor``.  0 with a zero gradient
+    when no point is labelled."""
+    N, K = logits.shape
+    if N == 0:
+        return logits.sum() * 0.0
+    lab = _imgseg_labels(labels, K).view(1, N, 1, 1)
+    x5 = logits.contiguous().view(1, N, 1, 1, K).permute(0, 4, 1, 2, 3)
+    if _point_head_fused(logits):
+        return lovasz_softmax(x5, lab, ignore=0)
+    from .plugin import losses
+    return losses.lovasz_softmax_tensor(x5, lab, 0)
+
+
+OCC_TAIL =os.environ.get("SSBEV_OCC_TAIL", "1") != "0"     # scalar loss algebra in one launch (0 = ~110 tiny ATen ops)
 
 
 class _OccLossTail(torch.autograd.Function):

@@ -16,7 +16,8 @@ def image_branch_cfg(arch="b7"):
 
 def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False, loss_depth_type="bce", voxel_ohem=0.0,
               ohem_topk=0.25, frustum_dist=0.0, voxel_dice=0.0, voxel_lga=0.0, imgseg=False, loss_seg_weight=1.0,
-              lift_with_imgseg=False, imgseg_labels="img_seg", crp3d=False, crp_level=2, point_xyz_channel=0, point_xyz_mode="cat"):
+              lift_with_imgseg=False, imgseg_labels="img_seg", crp3d=False, crp_level=2, point_xyz_channel=0, point_xyz_mode="cat",
+              supervise_points=False, sampling_img_feats=True, soft_weights=True, point_axis_order="reference"):
     """Same structure and hyper-parameters as the reference config's ``model`` dict for the sizes in ``cfg`` (a
     synthetic.CFG_*).  ``image_branch=False`` (default, the benchmarked hot path a1-a16) leaves the 2-D
     image backbone/neck out: the detector then takes the image-neck features in place of raw images.  ``loss_depth_type``:
@@ -33,7 +34,10 @@ def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False, 
     ``crp_level`` (on that stage's grid: ``crp_size``) and adds ``loss_rel_ce``; the training call then needs ``CP_mega_labels``
     (pipelines.CreateRelationLabels(relations=True)) or a dense ``CP_mega_matrix``.  ``point_xyz_channel`` > 0 (a multiple of 8)
     pools a learned encoding of every lifted point's position next to the features (``point_xyz_mode`` "cat": the 3-D encoder
-    takes that many more channels; "add": the width is ``numC_Trans`` and the encoding is added), fp32 only."""
+    takes that many more channels; "add": the width is ``numC_Trans`` and the encoding is added), fp32 only.
+    ``supervise_points=True`` builds the head's point-level branch (``sampling_img_feats`` / ``soft_weights``: the reference
+    config's values by default; ``point_axis_order`` "reference" or "xyz", see ``OccHead``) and adds ``loss_point_ce_`` /
+    ``loss_point_lovasz_``; the training call then needs ``points_occ`` and ``points_uv`` (pipelines.CreateDepthFromLiDAR)."""
     seg = dict(imgseg=True, imgseg_class=20, loss_seg_weight=float(loss_seg_weight), lift_with_imgseg=bool(lift_with_imgseg)) \
         if imgseg else {}
     bev_in = numC_Trans + (20 if imgseg and lift_with_imgseg else 0)
@@ -61,8 +65,9 @@ def model_cfg(cfg, numC_Trans=128, warp_align_corners=True, image_branch=False, 
         img_bev_encoder_neck=dict(type="SECONDFPN3D", norm_cfg=norm_cfg, in_channels=channels,
                                   upsample_strides=[1, 2, 4], out_channels=[128, 128, 128]),
         pts_bbox_head=dict(type="OccHead", num_level=1, in_channels=[384], out_channel=20, semantic_kitti=True,
-                           point_cloud_range=list(cfg["pc_range"]), supervise_points=False,
-                           sampling_img_feats=True, in_img_channels=640, soft_weights=True,
+                           point_cloud_range=list(cfg["pc_range"]), supervise_points=bool(supervise_points),
+                           sampling_img_feats=bool(sampling_img_feats), in_img_channels=640, soft_weights=bool(soft_weights),
+                           **(dict(point_axis_order=point_axis_order) if supervise_points else {}),
                            **(dict(use_ohem_loss=True, ohem_topk=ohem_topk) if voxel_ohem > 0 else {}),
                            **(dict(use_frustum_loss=True) if frustum_dist > 0 else {}),
                            **(dict(use_dice_loss=True) if voxel_dice > 0 else {}),

@@ -66,8 +66,16 @@ class BEVDepthOccupancy(nn.Module):
         voxel_feats, depth, img_feats = self.extract_img_feat(img, img_metas)
         return voxel_feats, img_feats, depth
 
-    def forward_pts_train(self, voxel_feats, gt_occ, points_occ=None, img_metas=None, **kwargs):
-        outs = self.pts_bbox_head(voxel_feats=voxel_feats, points=points_occ, img_metas=img_metas)
+    def _point_kwargs(self, img_feats, points_uv):
+        """``img_feats`` / ``points_uv`` for a head with the point-level branch (DET:140-146); any other head keeps the
+        three-argument call."""
+        if getattr(self.pts_bbox_head, "supervise_points", False):
+            return dict(img_feats=img_feats, points_uv=points_uv)
+        return {}
+
+    def forward_pts_train(self, voxel_feats, gt_occ, points_occ=None, img_metas=None, img_feats=None, points_uv=None, **kwargs):
+        outs = self.pts_bbox_head(voxel_feats=voxel_feats, points=points_occ, img_metas=img_metas,
+                                  **self._point_kwargs(img_feats, points_uv))
         return self.pts_bbox_head.loss(output_voxels=outs["output_voxels"], target_voxels=gt_occ,
                                        output_points=outs["output_points"], target_points=points_occ,
                                        img_metas=img_metas, **kwargs)       # DET:138-175: frustums_ids / _class_dists, ...
@@ -93,12 +101,14 @@ class BEVDepthOccupancy(nn.Module):
         if with_crp:                                                                                   # DET:238-241
             losses["loss_rel_ce"] = bev.crp_loss(CP_mega_matrices=kwargs.get("CP_mega_matrix"),
                                                  CP_mega_labels=kwargs.get("CP_mega_labels"))
-        losses.update(self.forward_pts_train(voxel_feats, gt_occ, points_occ, img_metas, **kwargs))
+        losses.update(self.forward_pts_train(voxel_feats, gt_occ, points_occ, img_metas, img_feats=img_feats,
+                                             points_uv=points_uv, **kwargs))
         return losses
 
     def simple_test(self, img_metas=None, img=None, rescale=False, points_occ=None, gt_occ=None, points_uv=None):
         voxel_feats, img_feats, depth = self.extract_feat(points=None, img=img, img_metas=img_metas)
-        out = self.pts_bbox_head(voxel_feats=voxel_feats, points=points_occ, img_metas=img_metas)
+        out = self.pts_bbox_head(voxel_feats=voxel_feats, points=points_occ, img_metas=img_metas,
+                                 **self._point_kwargs(img_feats, points_uv))
         out["evaluation_semantic"] = 0
         from ..functional import upsample_trilinear
         out["output_voxels"] = upsample_trilinear(out["output_voxels"][0], gt_occ.shape[1:])

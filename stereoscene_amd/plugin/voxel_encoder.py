@@ -141,22 +141,66 @@ class SECONDFPN3D(nn.Module):
         return [torch.cat(ups, dim=1) if len(ups) > 1 else ups[0]]
 
 
+class Mlp(nn.Module):
+    """``fc1 -> GELU (exact, erf) -> fc2`` (dense_heads/mlp.py; dropout 0): the reference's keys ``fc1.*`` / ``fc2.*``, both
+    products on the own GEMM kernels (``functional.small_linear``)."""
+
+    def __init__(self, in_features, hidden_features=None, out_features=None):
+        super().__init__()
+        self.fc1 = nn.Linear(in_features, hidden_features or in_features)
+        self.fc2 = nn.Linear(hidden_features or in_features, out_features or in_features)
+
+    def forward(self, x):
+        h = torch.nn.functional.gelu(F.small_linear(x, self.fc1.weight, self.fc1.bias))
+        return F.small_linear(h, self.fc2.weight, self.fc2.bias)
+
+
 @HEADS.register_module()
 class OccHead(nn.Module):
+    """``supervise_points=True`` builds the point-level branch (occhead.py:110-133, 171-236, 363-398): every labelled LiDAR
+    point samples the first ``num_level`` voxel feature maps trilinearly and, with ``sampling_img_feats``, the left view's image
+    features bilinearly at its projection; ``soft_weights`` mixes the row sets with a learned softmax, ``point_occ_mlp`` gives
+    the logits, and ``loss`` adds ``loss_point_ce_`` and ``loss_point_lovasz_`` (weights ``loss_weight_cfg.loss_point_ce_weight``
+    / ``.loss_point_lovasz_weight``, both 1 by default).  ``point_axis_order``: "reference" hands (x, y, z) to the sampler as the
+    reference does, so that a point's x walks the Z axis and its z the X axis (``functional.point_sample_tensor``); "xyz" samples
+    X with x, Y with y and Z with z.  Without a labelled point both losses are exactly 0 (the reference's CE is NaN); samples
+    of one point work (the reference's ``.squeeze().t()`` breaks on them).  fp32 only."""
+
     def __init__(self, in_channels, out_channel, out_point_channel=None, semantic_kitti=False, supervise_voxel=True,
                  num_level=1, num_img_level=1, in_img_channels=512, sampling_img_feats=False, soft_weights=False,
                  supervise_points=False, loss_weight_cfg=None, semkitti_loss_weight_cfg=None,
                  loss_voxel_prototype="cylinder3d", use_ohem_loss=False, use_sc_ohem_loss=False, ohem_topk=0.25,
                  conv_cfg=dict(type="Conv3d", bias=False), norm_cfg=dict(type="GN", num_groups=32, requires_grad=True),
                  point_cloud_range=(-51.2, -51.2, -5.0, 51.2, 51.2, 3.0), with_cp=False, train_cfg=None, test_cfg=None,
-                 use_frustum_loss=False, use_dice_loss=False, use_lga_loss=False):
+                 use_frustum_loss=False, use_dice_loss=False, use_lga_loss=False, point_axis_order="reference"):
         super().__init__()
-        if supervise_points or not semantic_kitti or not supervise_voxel:
+        if not semantic_kitti or not supervise_voxel:
             raise NotImplementedError("only the voxel-supervised SemanticKITTI head used by the config is built")
         self.in_channels = list(in_channels) if isinstance(in_channels, (list, tuple)) else [in_channels]
         self.out_channel, self.num_level = out_channel, num_level
-        self.semantic_kitti, self.supervise_voxel, self.supervise_points = True, True, False
+        self.semantic_kitti, self.supervise_voxel, self.supervise_points = True, True, bool(supervise_points)
         self.point_cloud_range = torch.tensor(np.array(point_cloud_range))
+        if self.supervise_points:
+            if point_axis_order not in F.POINT_AXIS_ORDERS:
+                raise ValueError(f"point_axis_order must be one of {F.POINT_AXIS_ORDERS}, got {point_axis_order!r}")
+            if F.storage_bf16():
+                raise NotImplementedError("supervise_points=True runs in fp32 only: the point kernels have no bf16 storage form")
+            if len(set(self.in_channels[:num_level])) != 1:
+                raise NotImplementedError("the point-level branch adds the levels' rows: they must have one width")
+            self.point_axis_order = point_axis_order
+            self.soft_weights, self.sampling_img_feats = bool(soft_weights), bool(sampling_img_feats)
+            self.num_img_level, self.in_img_channels = num_img_level, in_img_channels
+            c0 = self.in_channels[0]
+            if self.sampling_img_feats:
+                self.img_feat_reduce = nn.Linear(in_img_channels, c0)
+            self.num_point_sampling_feat = num_level + int(self.sampling_img_feats) * num_img_level
+            if self.soft_weights:
+                self.point_soft_weights = nn.Sequential(nn.Linear(c0, c0 // 2), nn.ReLU(inplace=True),
+                                                        nn.Linear(c0 // 2, self.num_point_sampling_feat))
+            self.point_occ_mlp = Mlp(self.in_channels[-1], self.in_channels[-1], out_point_channel or out_channel)
+            lw = loss_weight_cfg or {}
+            self.loss_point_ce_weight = float(lw.get("loss_point_ce_weight", 1.0))
+            self.loss_point_lovasz_weight = float(lw.get("loss_point_lovasz_weight", 1.0))
         self.occ_convs = nn.ModuleList()
         for i in range(num_level):
             mid = self.in_channels[i] // 2
@@ -197,9 +241,68 @@ class OccHead(nn.Module):
     def forward_voxel(self, voxel_feats):
         return [conv(f) for f, conv in zip(voxel_feats, self.occ_convs)]
 
+    def sample_point_feats(self, points, voxel_feats, img_feats=None, points_uv=None):
+        """occhead.py:171-236 for the whole batch at once: ``points`` list of [N_b, >= 3], ``points_uv`` list of [N_b, cams, 3],
+        ``img_feats`` [B, cams, C_img, fH, fW] -> rows [sum N_b, C].  The row-wise layers run on the concatenation (same
+        arithmetic per row); the second soft-weight Linear has ``num_point_sampling_feat`` (2 in the config) output rows, which
+        are zero-padded to a multiple of 4 so that this product stays on the own GEMM kernels too."""
+        counts = [int(p.shape[0]) for p in points]
+        g = F.point_unit(torch.cat([p[:, :3].float() for p in points], 0), self.point_cloud_range.tolist())
+        feats = list(voxel_feats[:self.num_level])
+        g = g.to(feats[0].device)
+        sets = list(F.point_sample(feats, g, counts, self.point_axis_order, per_level=self.soft_weights).unbind(0)) \
+            if self.soft_weights else [F.point_sample(feats, g, counts, self.point_axis_order)]
+        if self.sampling_img_feats:
+            uv = torch.cat([u.float() for u in points_uv], 0).to(g.device)
+            rows = F.point_img_sample(img_feats, uv, counts)
+            sets.append(F.small_linear(rows, self.img_feat_reduce.weight, self.img_feat_reduce.bias))
+        if not self.soft_weights:
+            return sum(sets[1:], sets[0])
+        fc1, fc2 = self.point_soft_weights[0], self.point_soft_weights[2]
+        nl = fc2.out_features
+        pad = -nl % 4
+        h = torch.relu(F.small_linear(sets[0], fc1.weight, fc1.bias))
+        w = F.small_linear(h, torch.nn.functional.pad(fc2.weight, (0, 0, 0, pad)), torch.nn.functional.pad(fc2.bias, (0, pad)))
+        w = torch.softmax(w[:, :nl], dim=1)
+        out = 0
+        for rows, wl in zip(sets, torch.unbind(w, dim=1)):
+            out = out + rows * wl.unsqueeze(1)
+        return out
+
+    def forward_points(self, points, voxel_feats, img_feats=None, points_uv=None):
+        counts = [int(p.shape[0]) for p in points]
+        K = self.point_occ_mlp.fc2.out_features
+        if sum(counts) == 0:
+            zero = sum((p * 0).sum() for p in self.parameters())
+            return [voxel_feats[0].new_zeros(0, K) + zero for _ in counts]
+        logits = self.point_occ_mlp(self.sample_point_feats(points, voxel_feats, img_feats, points_uv))
+        return list(torch.split(logits, counts, 0))
+
     def forward(self, voxel_feats, points=None, img_metas=None, img_feats=None, points_uv=None, **kwargs):
         assert type(voxel_feats) is list and len(voxel_feats) == self.num_level
-        return {"output_voxels": self.forward_voxel(voxel_feats), "output_points": None}
+        output_points = None
+        if self.supervise_points:
+            missing = [n for n, v in (("points_occ", points), ("points_uv", points_uv if self.sampling_img_feats else 0))
+                       if v is None]
+            if missing and (self.training or points is not None):
+                raise KeyError(f"supervise_points=True needs the kwargs {missing} (pipelines.CreateDepthFromLiDAR + "
+                               "OccDefaultFormatBundle3D provide them)")
+            if self.sampling_img_feats and points is not None and img_feats is None:
+                raise KeyError("sampling_img_feats=True needs 'img_feats' (the detector passes the left view's neck output)")
+            if points is not None:
+                output_points = self.forward_points(points, voxel_feats, img_feats, points_uv)
+        return {"output_voxels": self.forward_voxel(voxel_feats), "output_points": output_points}
+
+    def loss_point_single(self, output_points, target_points, tag=""):
+        """occhead.py:363-398 with ``semantic_kitti=True`` (no ``point_mean_iou``): labels = ``target_points[:, -1]``, class 0
+        ignored; both losses exactly 0 with zero gradients when no point is labelled."""
+        labels = target_points[:, -1].to(output_points.device)
+        out = {}
+        if self.loss_point_ce_weight > 0:
+            out[f"loss_point_ce_{tag}"] = F.point_ce_loss(output_points, labels) * self.loss_point_ce_weight
+        if self.loss_point_lovasz_weight > 0:
+            out[f"loss_point_lovasz_{tag}"] = F.point_lovasz_loss(output_points, labels) * self.loss_point_lovasz_weight
+        return out
 
     def loss_voxel_single_semkitti(self, output_voxels, target_voxels, tag, compute_metric=False, **kwargs):
         w = self.semkitti_loss_weight_cfg
@@ -217,4 +320,8 @@ class OccHead(nn.Module):
         out = {}
         for i, o in enumerate(output_voxels):
             out.update(self.loss_voxel_single_semkitti(o, targets[i], tag=str(i), compute_metric=(i == 0), **kwargs))
+        if self.supervise_points:
+            if output_points is None or target_points is None:
+                raise KeyError("supervise_points=True needs 'points_occ' (output_points / target_points) in loss()")
+            out.update(self.loss_point_single(torch.cat(output_points, 0), torch.cat(list(target_points), 0), tag=""))
         return out

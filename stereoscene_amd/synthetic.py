@@ -558,6 +558,78 @@ def point_xyz_case(name):
                 G=hash_uniform(f"{tag}/G", (B, Cx, n[0], n[1], n[2]), -1.0, 1.0))
 
 
+# Cases of the point-level branch (tools/make_golden_point_head.py records the float64 result on them): name -> dict(counts = points
+# per sample, C = level width, grids = the levels' (X, Y, Z), soft = soft_weights, cams = cameras of the image branch (0: none),
+# axis = point_axis_order, kind = how the points are drawn).  A: all inside; B: unequal axes, points up to 0.6 of the range outside
+# on every side (1.5 cells and more), exactly on the range's faces and on cell centres; C1 / C2: two levels, soft weights, image
+# features [cams, 12, 3, 5] with uv exactly +-1, depth at and below 1e-5 and uv outside; D: 600 points in one cell of 256;
+# E: an empty and a single-point sample; F: B sampled in xyz order; G: C1 with every label 0.
+POINT_HEAD_RANGE = (0.0, -4.0, -1.0, 8.0, 4.0, 3.0)
+POINT_HEAD_CLASSES = 20
+POINT_HEAD_IMG = (12, 3, 5)
+POINT_HEAD_CASES = {
+    "A": dict(counts=(37,), C=8, grids=((4, 4, 2),), soft=False, cams=0, axis="reference", kind="inside"),
+    "B": dict(counts=(5, 130), C=40, grids=((6, 5, 3),), soft=False, cams=0, axis="reference", kind="edges"),
+    "C1": dict(counts=(40, 23), C=16, grids=((8, 8, 4), (4, 4, 2)), soft=True, cams=1, axis="reference", kind="edges"),
+    "C2": dict(counts=(40, 23), C=16, grids=((8, 8, 4), (4, 4, 2)), soft=True, cams=2, axis="reference", kind="edges"),
+    "D": dict(counts=(600,), C=8, grids=((8, 8, 4),), soft=False, cams=0, axis="reference", kind="one_cell"),
+    "E": dict(counts=(0, 1), C=8, grids=((4, 4, 2),), soft=False, cams=0, axis="reference", kind="inside"),
+    "F": dict(counts=(5, 130), C=40, grids=((6, 5, 3),), soft=False, cams=0, axis="xyz", kind="edges"),
+    "G": dict(counts=(40, 23), C=16, grids=((8, 8, 4), (4, 4, 2)), soft=True, cams=1, axis="reference", kind="edges", labels="zero"),
+}
+POINT_HEAD_ORDER = ("A", "B", "C1", "C2", "D", "E", "F", "G")
+
+
+def point_head_case(name):
+    """dict of a POINT_HEAD_CASES entry: spec, head_kwargs (for ``OccHead``; parameters: ``fill_state_dict_``), feats (list of
+    fp32 [B, C, X, Y, Z]), points (list of fp32 [N_b, 4] = x, y, z, label), img_feats (fp32 [B, cams, 12, 3, 5] or None) and
+    points_uv (list of fp32 [N_b, cams, 3] or None), all hash-generated."""
+    spec = POINT_HEAD_CASES[name]
+    src = {"F": "B", "G": "C1"}.get(name, name)                     # F and G reuse the inputs of B and C1
+    tag = f"point_head/{src}"
+    counts, C_, B = spec["counts"], spec["C"], len(spec["counts"])
+    lo = torch.tensor(POINT_HEAD_RANGE[:3])
+    rng = torch.tensor(POINT_HEAD_RANGE[3:]) - lo
+    X, Y, Z = spec["grids"][0]
+    points, uvs = [], []
+    for b, n in enumerate(counts):
+        if spec["kind"] == "inside":
+            g = hash_uniform(f"{tag}/g{b}", (n, 3), -0.999, 0.999)
+        elif spec["kind"] == "edges":
+            g = hash_uniform(f"{tag}/g{b}", (n, 3), -1.6, 1.6)
+            for i in range(min(n, 24)):                            # the first rows: faces of the range and cell centres
+                if i % 4 == 0:
+                    g[i, i // 4 % 3] = 1.0 if i % 8 else -1.0
+                elif i % 4 == 1:
+                    cell = torch.tensor([i % X, i % Y, i % Z], dtype=torch.float32)
+                    g[i] = (2 * cell + 1) / torch.tensor([X, Y, Z], dtype=torch.float32) - 1
+        else:                                                       # every point within 0.4 cells of one grid corner: eight long lists
+            g = torch.tensor([0.375, -0.125, 0.375]) + hash_uniform(f"{tag}/g{b}", (n, 3), -0.1, 0.1)
+        p = lo + (g + 1) / 2 * rng
+        hit = torch.isclose(g, torch.ones(())) | torch.isclose(g, -torch.ones(()))
+        p = torch.where(hit & (g > 0), lo + rng, torch.where(hit, lo.expand_as(p), p))      # exactly on the faces: g = +-1 exactly
+        lab = (hash_uniform(f"{tag}/lab{b}", (n,), 0.0, 1.0) * POINT_HEAD_CLASSES).floor().clamp_(0, POINT_HEAD_CLASSES - 1)
+        if spec.get("labels") == "zero":
+            lab = torch.zeros(n)
+        points.append(torch.cat((p, lab[:, None]), 1))
+        if spec["cams"]:
+            uv = torch.cat((hash_uniform(f"{tag}/uv{b}", (n, spec["cams"], 2), -1.3, 1.3),
+                            hash_uniform(f"{tag}/d{b}", (n, spec["cams"], 1), 0.5, 20.0)), -1)
+            special = [(1.0, 0.2, 5.0), (-1.0, 0.2, 5.0), (0.3, 1.0, 5.0), (0.3, -1.0, 5.0), (0.3, 0.2, 1e-5), (0.3, 0.2, 0.0),
+                       (0.3, 0.2, -2.0), (0.9999, -0.9999, 2e-5), (-0.95, 0.95, 5.0)]
+            for i, s in enumerate(special[:n]):
+                uv[i, i % spec["cams"]] = torch.tensor(s)
+            uvs.append(uv)
+    feats = [hash_normal(f"{tag}/feat{l}", (B, C_) + tuple(gr)) for l, gr in enumerate(spec["grids"])]
+    img = hash_normal(f"{tag}/img", (B, spec["cams"]) + POINT_HEAD_IMG) if spec["cams"] else None
+    head_kwargs = dict(in_channels=[C_] * len(spec["grids"]), out_channel=POINT_HEAD_CLASSES, semantic_kitti=True,
+                       num_level=len(spec["grids"]), supervise_points=True, soft_weights=spec["soft"],
+                       sampling_img_feats=bool(spec["cams"]), in_img_channels=POINT_HEAD_IMG[0],
+                       point_cloud_range=list(POINT_HEAD_RANGE), point_axis_order=spec["axis"],
+                       norm_cfg=dict(type="GN", num_groups=2, requires_grad=True))
+    return dict(spec=spec, head_kwargs=head_kwargs, feats=feats, points=points, img_feats=img, points_uv=uvs if spec["cams"] else None)
+
+
 def synthetic_sample(cfg, B=1, C_in=640, tag="s0", with_targets=True):
     """Image-neck outputs for both views + geometry + targets, all hash-generated.
 
