@@ -813,6 +813,26 @@ typedef struct { int flags, mode; float delta, alpha, saturation, hue; int perm[
 int ssbev_crop_rotate_jitter_normalize_u8(const uint8_t* src, int Hs, int Ws, float* dst, int x0, int y0, int w, int h, int flip,
                                           const int32_t* affine6, const ssbev_jitter_params* jitter, const float* mean,
                                           const float* stdinv, int swap_rb, ssbev_stream_t stream);
+/* BEV augmentation of the voxel labels (since ssbev_version() 120; loading_semkitti.py:304-356 bev_transform; csrc/bev_augment.hip):
+ * src uint8 [X,Y,Z] -> dst [X,Y,Z] (int64, or uint8 for the _u8 form): scipy.ndimage.rotate(order=0, mode='constant', cval=fill,
+ * axes=(0,1), reshape=False), then the flip of axis 1 (flip_dy), then the flip of axis 0 (flip_dx).
+ * coeffs6 = {m00, m01, m10, m11, off0, off1} (HOST pointer, doubles; scipy's own matrix [[c, s], [-s, c]] and offset, composed by
+ * the caller): output (i, j) of a plane samples ci = (m00*i + m01*j) + off0, cj = (m10*i + m11*j) + off1 -- IEEE double, every
+ * product and sum rounded on its own, no FMA -- and takes source voxel (floor(ci + 0.5), floor(cj + 0.5)) iff 0 <= ci <= X-1
+ * and 0 <= cj <= Y-1, else `fill`.  coeffs6 == NULL: no rotation (flips and widening alone; no workspace).
+ * inplace != 0 reproduces the upstream's rotate(lab, output=lab): scipy writes a plane in raster order p = i*Y + j over the array
+ * it reads, so an output whose source index is BELOW p takes the value already written there, out[p] = out[m[p]].  These chains
+ * are collapsed by pointer jumping in ceil(log2(X*Y)) rounds on a table of X*Y int32 (a count fixed by the dims: no read-back,
+ * the same bits every run).  inplace == 0 is the out-of-place rotation.  src and dst must not overlap in either form.
+ * ws: ssbev_bev_label_workspace bytes (rotate = whether coeffs6 is given), caller-owned.
+ * SSBEV_EINVAL before any device work: NULL src / dst (or ws with coeffs6), X, Y or Z < 1, X*Y > 2^31 - 3 (the int32 table),
+ * more than 2^31 - 1 blocks of 256 voxels, a non-finite coefficient, fill outside 0 .. 255, overlapping src and dst;
+ * SSBEV_EWORKSPACE: ws_bytes below the query. */
+size_t ssbev_bev_label_workspace(int X, int Y, int rotate, int inplace);
+int ssbev_bev_label_transform(const uint8_t* src, int64_t* dst, int X, int Y, int Z, const double* coeffs6, int inplace,
+                              int flip_dx, int flip_dy, int fill, void* ws, size_t ws_bytes, ssbev_stream_t stream);
+int ssbev_bev_label_transform_u8(const uint8_t* src, uint8_t* dst, int X, int Y, int Z, const double* coeffs6, int inplace,
+                                 int flip_dx, int flip_dy, int fill, void* ws, size_t ws_bytes, ssbev_stream_t stream);
 /* Depth BCE loss (ViewTransformerLSSVoxel.py:349-416: get_downsampled_gt_depth + get_depth_loss): gt_depths [BN, fH*ds, fW*ds]
  * (0 = no LiDAR return), depth_pred [BN, D, fH, fW] (a probability distribution over the D bins per pixel).  out2[0] = weight *
  * sum of the binary cross entropies over the pixels that have a return / max(their number, 1), out2[1] = that divisor.  The

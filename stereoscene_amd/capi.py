@@ -246,6 +246,9 @@ SIGNATURES = {
                                                 C.c_int, _P]),
     "ssbev_crop_rotate_jitter_normalize_u8": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P,
                                                        C.POINTER(JitterParams), _P, _P, C.c_int, _P]),
+    "ssbev_bev_label_workspace": (C.c_size_t, [C.c_int] * 4),
+    "ssbev_bev_label_transform": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)] + [C.c_int] * 4 + [_P, C.c_size_t, _P]),
+    "ssbev_bev_label_transform_u8": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)] + [C.c_int] * 4 + [_P, C.c_size_t, _P]),
     "ssbev_depth_bce_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "ssbev_depth_bce_fwd": (C.c_int, [_P, _P, _P] + [C.c_int] * 5 + [C.c_float] * 3 + [_P, C.c_size_t, _P]),
     "ssbev_depth_bce_bwd": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [C.c_float] * 3 + [_P, _P]),

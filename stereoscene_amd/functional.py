@@ -2616,6 +2616,34 @@ def frustum_labels(labels, view, point_cloud_range, frustum_size=8):
 
 
 # -------------------------------------------------------------------------------------------------
+# BEV augmentation of the voxel labels (csrc/bev_augment.hip)
+# -------------------------------------------------------------------------------------------------
+SSBEV_BDA = os.environ.get("SSBEV_BDA", "1") != "0"          # loader's BEV label augmentation on the GPU (0 = the host form: scipy, then one upload)
+
+
+def bev_label_transform(labels_u8, coeffs, flip_dx, flip_dy, inplace=True, fill=255, out_dtype=torch.int64):
+    """``pipelines.bev_transform``'s label half on the GPU: uint8 labels [X,Y,Z] rotated in every (X, Y) plane by scipy's
+    order-0 ``mode='constant'`` rule (``coeffs`` = scipy's own ``(m00, m01, m10, m11, off0, off1)`` as Python floats, composed
+    by the caller in double; ``None`` = no rotation), then flipped along axis 1 (``flip_dy``) and axis 0 (``flip_dx``).
+    ``inplace=True`` reproduces the upstream's ``rotate(lab, output=lab)``, which reads voxels it has already overwritten;
+    ``inplace=False`` is the out-of-place rotation.  Returns int64 (or uint8 with ``out_dtype=torch.uint8``) [X,Y,Z]."""
+    if labels_u8.dtype != torch.uint8 or labels_u8.dim() != 3:
+        raise capi.SsbevError(f"bev_label_transform: uint8 [X,Y,Z] labels expected, got {labels_u8.dtype} {tuple(labels_u8.shape)}")
+    if out_dtype not in (torch.int64, torch.uint8):
+        raise ValueError(f"bev_label_transform: out_dtype must be torch.int64 or torch.uint8, got {out_dtype}")
+    lib = capi.load()
+    lab = labels_u8.contiguous()
+    X, Y, Z = (int(v) for v in lab.shape)
+    out = torch.empty(X, Y, Z, dtype=out_dtype, device=lab.device)
+    c6 = None if coeffs is None else (C.c_double * 6)(*(float(v) for v in coeffs))
+    ws = _ws(lib.ssbev_bev_label_workspace(X, Y, int(c6 is not None), int(bool(inplace))), lab.device)
+    fn = lib.ssbev_bev_label_transform if out_dtype == torch.int64 else lib.ssbev_bev_label_transform_u8
+    capi.check(fn(capi.ptr(lab), capi.ptr(out), X, Y, Z, c6, int(bool(inplace)), int(bool(flip_dx)), int(bool(flip_dy)), int(fill),
+                  capi.ptr(ws), ws.numel(), capi.stream()), "ssbev_bev_label_transform")
+    return out
+
+
+# -------------------------------------------------------------------------------------------------
 # 3-D context relation prior (csrc/crp.hip): label down-sampling, relation matrix, relation loss, relation gather
 # -------------------------------------------------------------------------------------------------
 CRP = os.environ.get("SSBEV_CRP", "1") != "0"                # fused relation loss and gather (0 = the tensor forms: sigmoid, bmm, cat, BCEWithLogits)

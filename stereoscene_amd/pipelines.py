@@ -543,10 +543,42 @@ class LoadMultiViewImageFromFiles_SemanticKitti:
         return results
 
 
-def bev_transform(voxel_labels, rotate_angle, scale_ratio, flip_dx, flip_dy, transform_center):
+BDA_ROTATE_MODES = ("reference", "exact")
+
+
+def _scipy_ndimage():
+    try:
+        import scipy.ndimage
+        import scipy.special
+    except ImportError as e:
+        raise ImportError("the BEV label rotation (bev_transform with a non-zero angle) needs scipy: the host form calls "
+                          "scipy.ndimage.rotate, the device form takes scipy.special.cosdg / sindg for its coefficients") from e
+    return scipy
+
+
+def bev_rotate_coeffs(X, Y, angle):
+    """The source map of ``scipy.ndimage.rotate(a, angle, axes=(0, 1), reshape=False)`` on an X x Y plane, composed as scipy
+    composes it, in double: ``(m00, m01, m10, m11, off0, off1)`` with output (i, j) sampling ``M @ (i, j) + off``.
+    ``cosdg`` / ``sindg`` are exact at the multiples of 90 degrees, which ``np.cos`` of radians is not."""
+    special = _scipy_ndimage().special
+    c, s = special.cosdg(angle), special.sindg(angle)
+    m = np.array([[c, s], [-s, c]])
+    centre = (np.asarray([X, Y]) - 1) / 2
+    off = centre - m @ centre
+    return tuple(float(v) for v in (m[0, 0], m[0, 1], m[1, 0], m[1, 1], off[0], off[1]))
+
+
+def bev_transform(voxel_labels, rotate_angle, scale_ratio, flip_dx, flip_dy, transform_center, device=None, rotate_mode="reference"):
     """BEV augmentation of the voxel labels and its 4x4 matrix about the centre of the point-cloud range
     (loading_semkitti.py:304-356): ``denorm @ flip_x @ flip_y @ rot @ norm``; labels rotated with nearest-neighbour
-    resampling (fill 255) and flipped.  ``scale_ratio`` is drawn but unused upstream."""
+    resampling (fill 255) and flipped.  ``scale_ratio`` is drawn but unused upstream.
+    ``rotate_mode="reference"`` is the upstream's rotation IN PLACE (``rotate(lab, output=lab)``): scipy does not guard against
+    that aliasing, walks each (X, Y) plane in raster order and reads voxels it has already overwritten, so close to half of the
+    grid differs from a true rotation -- that grid is what the upstream trains on.  ``"exact"`` rotates out of place.
+    ``device``: a CUDA device runs the label half there (``functional.bev_label_transform``: the labels go up as uint8, int64
+    labels come back on the device, the same bytes as the host form); ``None`` is the host form.  The matrix stays on the host."""
+    if rotate_mode not in BDA_ROTATE_MODES:
+        raise ValueError(f"bev_transform: rotate_mode must be one of {BDA_ROTATE_MODES}, got {rotate_mode!r}")
     trans_norm, trans_denorm = torch.eye(4), torch.eye(4)
     trans_norm[:3, -1] = -transform_center
     trans_denorm[:3, -1] = transform_center
@@ -559,10 +591,21 @@ def bev_transform(voxel_labels, rotate_angle, scale_ratio, flip_dx, flip_dy, tra
     if flip_dy:
         flip_mat = flip_mat @ torch.diag(torch.Tensor([1, -1, 1, 1]))
     bda_mat = trans_denorm @ flip_mat @ rot_mat @ trans_norm
+    rotates = not np.isclose(rotate_angle, 0)
+    if device is not None and torch.device(device).type == "cuda":
+        from . import functional as F
+        lab = voxel_labels.to(torch.uint8) if voxel_labels.is_cuda else torch.from_numpy(voxel_labels.numpy().astype(np.uint8))
+        coeffs = bev_rotate_coeffs(lab.shape[0], lab.shape[1], rotate_angle) if rotates else None
+        lab = lab.to(device)
+        return F.bev_label_transform(lab, coeffs, flip_dx, flip_dy, inplace=rotate_mode == "reference"), bda_mat
     lab = voxel_labels.numpy().astype(np.uint8)
-    if not np.isclose(rotate_angle, 0):
-        import scipy.ndimage
-        scipy.ndimage.rotate(lab, rotate_angle, output=lab, mode="constant", order=0, cval=255, axes=(0, 1), reshape=False)
+    if rotates:
+        ndimage = _scipy_ndimage().ndimage
+        kw = dict(mode="constant", order=0, cval=255, axes=(0, 1), reshape=False)
+        if rotate_mode == "reference":
+            ndimage.rotate(lab, rotate_angle, output=lab, **kw)
+        else:
+            lab = ndimage.rotate(lab, rotate_angle, **kw)
     if flip_dy:
         lab = lab[:, ::-1]
     if flip_dx:
@@ -573,10 +616,17 @@ def bev_transform(voxel_labels, rotate_angle, scale_ratio, flip_dx, flip_dy, tra
 @PIPELINES.register_module()
 class LoadSemKittiAnnotation:
     """Pipeline step of stereoscene.py:142 (loading_semkitti.py:358-402): turns ``results['gt_occ']`` into a tensor,
-    optionally applies the BEV augmentation, and inserts the BEV matrix as slot 6 of both views' ``img_inputs``."""
+    optionally applies the BEV augmentation, and inserts the BEV matrix as slot 6 of both views' ``img_inputs``.
+    ``device``: a CUDA device runs the label augmentation of a train sample there and leaves ``gt_occ`` on it (``bev_transform``;
+    ``SSBEV_BDA=0``: the host form, then one upload); ``None`` is the host step.  ``bda_rotate``: ``bev_transform``'s
+    ``rotate_mode``.  The random draws and their order are the same on either path."""
 
-    def __init__(self, bda_aug_conf, is_train=True, apply_bda=False, point_cloud_range=(0, -25.6, -2, 51.2, 25.6, 4.4)):
+    def __init__(self, bda_aug_conf, is_train=True, apply_bda=False, point_cloud_range=(0, -25.6, -2, 51.2, 25.6, 4.4), device=None,
+                 bda_rotate="reference"):
+        if bda_rotate not in BDA_ROTATE_MODES:
+            raise ValueError(f"LoadSemKittiAnnotation: bda_rotate must be one of {BDA_ROTATE_MODES}, got {bda_rotate!r}")
         self.bda_aug_conf, self.is_train, self.apply_bda = bda_aug_conf, is_train, apply_bda
+        self.device, self.bda_rotate = device, bda_rotate
         self.point_cloud_range = torch.tensor(point_cloud_range)
         self.transform_center = (self.point_cloud_range[:3] + self.point_cloud_range[3:]) / 2
 
@@ -592,7 +642,14 @@ class LoadSemKittiAnnotation:
         gt_occ = [torch.tensor(x) for x in g] if type(g) is list else torch.tensor(g)
         if self.apply_bda:
             if self.is_train:
-                gt_occ, bda_rot = bev_transform(gt_occ, *self.sample_bda_augmentation(), self.transform_center)
+                # the labels of the augmented sample are born on `device` (SSBEV_BDA=0: on the host, then moved there)
+                on_gpu = self.device is not None and torch.device(self.device).type == "cuda"
+                if on_gpu:
+                    from . import functional as F
+                gt_occ, bda_rot = bev_transform(gt_occ, *self.sample_bda_augmentation(), self.transform_center,
+                                                device=self.device if on_gpu and F.SSBEV_BDA else None, rotate_mode=self.bda_rotate)
+                if on_gpu and not gt_occ.is_cuda:
+                    gt_occ = gt_occ.to(self.device)
             else:
                 bda_rot = torch.eye(4)
         else:
