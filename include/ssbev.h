@@ -741,6 +741,10 @@ int ssbev_bn_update_running(const float* mean, const float* rstd, float* running
 int ssbev_softmax_axis_fwd(const float* x, float* y, int64_t outer, int C, int64_t inner, ssbev_stream_t stream);
 int ssbev_softmax_axis_bwd(const float* y, const float* gy, float* gx, int64_t outer, int C, int64_t inner,
                            ssbev_stream_t stream);
+/* Host-side query (since ssbev_version() 121; no device work): the kernel instance both launchers pick for this geometry, as the
+ * number of slices a column's axis is cut into across the threads of a workgroup: 8 (32 columns per workgroup) or 1 (256
+ * columns per workgroup); 0 for C <= 0 or inner <= 0. */
+int ssbev_softmax_axis_slices(int C, int64_t inner);
 /* Softmax along the innermost axis of `rows` rows of C contiguous floats (C % 4 == 0, C <= 8192): the BRI attention
  * matrix softmax(energy, -1) of attention.py:66-68 (T = 7680).  One read + one write of the matrix forward, two reads +
  * one write backward (gx = y * (gy - sum_c y * gy)); y may alias x and gx may alias gy. */
@@ -922,6 +926,12 @@ int ssbev_chan_sum(const float* a, const float* bmul, float* out, int B, int64_t
                    size_t ws_elems, ssbev_stream_t stream);
 int ssbev_chan_scale(const float* x, const float* gate, float* y, int B, int64_t S, int C, float scale,
                      ssbev_stream_t stream);
+/* Host-side queries (since ssbev_version() 121; no device work), from the functions the launchers themselves read:
+ *   bwd_weight_layout: a workgroup of ssbev_dwconv2d_bwd_weight is Q channel quads x L pixel lanes (Q * L <= 256), the channels
+ *                      take qblocks such workgroups per pixel chunk (the pixel chunks follow from the workspace query).
+ *   stream_blocks:     workgroups of the grid-stride passes (swish, chan_scale) over n4 float4 elements; 0 for n4 <= 0. */
+int ssbev_dwconv2d_bwd_weight_layout(const ssbev_dw_dims* d, int* Q, int* L, int* qblocks);
+int64_t ssbev_stream_blocks(int64_t n4);
 
 /* ---------------------------------------------------------------------------------------------
  * Winograd F(2x2x2, 3x3x3) transforms for stride-1 3x3x3 "same" convolutions (even D, H, W; channels-last).

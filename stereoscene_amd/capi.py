@@ -269,6 +269,8 @@ SIGNATURES = {
     "ssbev_chan_sum_workspace": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     "ssbev_chan_sum": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_float, _P, C.c_size_t, _P]),
     "ssbev_chan_scale": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_float, _P]),
+    "ssbev_dwconv2d_bwd_weight_layout": (C.c_int, [C.POINTER(DwDims), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ssbev_stream_blocks": (C.c_int64, [C.c_int64]),
     "ssbev_wino_input_transform": (C.c_int, [_P, _P, C.POINTER(WinoDims), _P]),
     "ssbev_wino_output_transform": (C.c_int, [_P, _P, C.POINTER(WinoDims), _P]),
     "ssbev_wino_output_adjoint": (C.c_int, [_P, _P, C.POINTER(WinoDims), _P]),
@@ -331,6 +333,7 @@ SIGNATURES = {
     "ssbev_wino2d_output_adjoint_bf16a": (C.c_int, [_P, _P, C.POINTER(WinoDims), _P]),
     "ssbev_softmax_axis_fwd": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int64, _P]),
     "ssbev_softmax_axis_bwd": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int64, _P]),
+    "ssbev_softmax_axis_slices": (C.c_int, [C.c_int, C.c_int64]),
     "ssbev_softmax_rows_fwd": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),
     "ssbev_softmax_rows_bwd": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P]),
     "ssbev_occ_loss_num_sums": (C.c_int, []),

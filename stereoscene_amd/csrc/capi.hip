@@ -29,7 +29,7 @@ const char* ssbev_env(const char* name) {
 }
 
 extern "C" {
-int ssbev_version(void) { return 120; /* 0.1.20: + ssbev_bev_label_* */ }
+int ssbev_version(void) { return 121; /* 0.1.21: + layout queries of the streaming operators */ }
 const char* ssbev_build_arch(void) { return "gfx950"; }
 
 // Forget every switch read so far: the next use of a name reads the environment again.  (Switches that a launch helper folded

@@ -301,6 +301,16 @@ size_t ssbev_dwconv2d_bwd_weight_workspace(const ssbev_dw_dims* d) {
   return (size_t)nchunks * d->k * d->k * d->C;          // floats
 }
 
+// host only: the thread layout ssbev_dwconv2d_bwd_weight launches with (dw_layout, which the launcher and dw_chunks read)
+int ssbev_dwconv2d_bwd_weight_layout(const ssbev_dw_dims* d, int* Q, int* L, int* qblocks) {
+  if (!dw_ok(d) || !Q || !L || !qblocks) return SSBEV_EINVAL;
+  dw_layout(d, Q, L, qblocks);
+  return SSBEV_OK;
+}
+
+// host only: workgroups of the grid-stride passes (swish, chan_scale) over n4 float4 elements
+int64_t ssbev_stream_blocks(int64_t n4) { return n4 > 0 ? (int64_t)stream_blocks((long)n4) : 0; }
+
 int ssbev_dwconv2d_bwd_weight(const float* x, const float* gy, float* gw, const ssbev_dw_dims* d, float* ws,
                               size_t ws_elems, ssbev_stream_t stream) {
   if (!dw_ok(d) || !x || !gy || !gw || !ws) return SSBEV_EINVAL;

@@ -147,13 +147,19 @@ softmax_row_bwd_kernel(const float* __restrict__ y, const float* gy, float* gx, 
   }
 }
 
+// slices of the softmax axis per column: long axes over wide enough maps are cut in 8, everything else walks its column alone
+int axis_slices(int C, long inner) { return C >= 64 && inner >= 32 ? 8 : 1; }
+
 }  // namespace
 
 extern "C" {
 
+// host only: the instance (slices per column, 8 or 1) ssbev_softmax_axis_fwd / _bwd launch for this geometry; 0 for bad arguments
+int ssbev_softmax_axis_slices(int C, int64_t inner) { return C > 0 && inner > 0 ? axis_slices(C, (long)inner) : 0; }
+
 int ssbev_softmax_axis_fwd(const float* x, float* y, int64_t outer, int C, int64_t inner, ssbev_stream_t stream) {
   if (!x || !y || outer <= 0 || C <= 0 || inner <= 0) return SSBEV_EINVAL;
-  if (C >= 64 && inner >= 32)
+  if (axis_slices(C, (long)inner) == 8)
     hipLaunchKernelGGL(softmax_axis_fwd_kernel<8>, dim3(cdiv((size_t)(outer * inner), 32)), dim3(256), 0, as_stream(stream),
                        x, y, (long)outer, C, (long)inner);
   else
@@ -165,7 +171,7 @@ int ssbev_softmax_axis_fwd(const float* x, float* y, int64_t outer, int C, int64
 int ssbev_softmax_axis_bwd(const float* y, const float* gy, float* gx, int64_t outer, int C, int64_t inner,
                            ssbev_stream_t stream) {
   if (!y || !gy || !gx || outer <= 0 || C <= 0 || inner <= 0) return SSBEV_EINVAL;
-  if (C >= 64 && inner >= 32)
+  if (axis_slices(C, (long)inner) == 8)
     hipLaunchKernelGGL(softmax_axis_bwd_kernel<8>, dim3(cdiv((size_t)(outer * inner), 32)), dim3(256), 0, as_stream(stream),
                        y, gy, gx, (long)outer, C, (long)inner);
   else
