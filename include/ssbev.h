@@ -900,6 +900,33 @@ int ssbev_lidar_depth_map(const float* points, int n_points, const float* cam, c
                           unsigned char* valid, float* depth, float* seg, int H, int W, void* ws, size_t ws_bytes,
                           ssbev_stream_t stream);
 
+/* CreateDepthFromOccupancy (since ssbev_version() 122; datasets/pipelines/occ_to_depth.py:15-153; csrc/occ_depth.hip): the depth
+ * map and the image-view label map of one view from the voxel labels alone.  labels uint8 [X][Y][Z] (device); xs [X], ys [Y],
+ * zs [Z] = the voxel centres per axis (device, fp32; the caller makes them with the reference's torch.arange, :36-38); cam46 = 46
+ * floats in HOST memory (copied into the launch: no synchronisation):
+ *   inv(bda)[:3] as 3x4 row major (column 3 ignored when bda_cols == 3) | inv(rots) 3x3 | trans 3 | intrins 4x4 | post_rots[:2,:2] |
+ *   post_trans[:2];  bda_cols = 3 or 4, the size of the BEV matrix (4: the centre is taken as [p; 1]).
+ * Every centre is projected with project_points' fp32 operation order (:43-65: inv_bda @ p, - trans, inv_rots @, intrins @ [p; 1],
+ * / depth, post_rots[:2,:2] @, + post_trans[:2]; every product and sum rounded on its own), is in view when 0 <= u <= W-1,
+ * 0 <= v <= H-1 and depth > 0 (:112-116), and lands on pixel (round-half-even(v), round-half-even(u)).
+ *   depth [H][W] = depth of the NEAREST in-view voxel labelled 1..254 per pixel, 0 where none (:121-127);
+ *   seg   [H][W] = label of the nearest in-view voxel per pixel, 255 where none (:132-140).  seg_occupied == 0 is the reference:
+ *                  EVERY in-view voxel competes, empty (0) and ignored (255) ones included, so an empty voxel in front of a
+ *                  surface takes the pixel; seg_occupied != 0 lets only labels 1..254 compete (the depth map's own voxels).
+ * Among voxels of a pixel with exactly equal fp32 depth the lowest flat index x*Y*Z + y*Z + z wins (the reference's argsort
+ * leaves it open); the result is the same bits every run.  ws: ssbev_occ_depth_workspace bytes, caller-owned (two key buffers).
+ * SSBEV_EINVAL before any device work: a NULL pointer (a table included), X, Y, Z, H or W < 1, more than 2^32 voxels, H*W above
+ * 2^31 - 257, bda_cols not 3 / 4; SSBEV_EWORKSPACE: ws_bytes below the query, which answers 0 for refused dims.
+ * ssbev_label_map_downsample: _downsample_label (:67-93) of a label map seg [H][W] (fp32 holding 0..255; anything else counts as
+ * 255) -> out [H/ds][W/ds] (trailing rows / columns dropped): a patch with more than empty_t (the caller's (float)(0.95*ds*ds))
+ * pixels 0 or 255 becomes 0 when the zeros outnumber the 255s, else 255; any other patch its most frequent label in 1..254, the
+ * LOWEST on a tie (torch.mode's choice).  1 <= ds <= 256. */
+size_t ssbev_occ_depth_workspace(int H, int W);
+int ssbev_occ_depth_map(const uint8_t* labels, int X, int Y, int Z, const float* xs, const float* ys, const float* zs,
+                        const float* cam46, int bda_cols, int seg_occupied, float* depth, float* seg, int H, int W, void* ws,
+                        size_t ws_bytes, ssbev_stream_t stream);
+int ssbev_label_map_downsample(const float* seg, float* out, int H, int W, int ds, float empty_t, ssbev_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Image branch (the step before a1/a5): operators of CustomEfficientNet (backbones/efficientnet.py:112-229,
  * 275-519: InvertedResidual = expand 1x1 -> depthwise k x k -> SE -> linear 1x1) that are not dense contractions.

@@ -16,7 +16,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # (hipcc's __fmul_rn/__fadd_rn are plain * and + and would otherwise fuse).
 PER_FILE_FLAGS = {"voxel_pool.hip": ["-ffp-contract=off"], "lidar_depth.hip": ["-ffp-contract=off"],
                   "bri_shell.hip": ["-ffp-contract=off"], "point_xyz.hip": ["-ffp-contract=off"],
-                  "bev_augment.hip": ["-ffp-contract=off"]}
+                  "bev_augment.hip": ["-ffp-contract=off"], "occ_depth.hip": ["-ffp-contract=off"]}
 
 
 def sources():

@@ -260,6 +260,10 @@ SIGNATURES = {
     "ssbev_imgseg_ce_bwd": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, _P, _P, _P]),
     "ssbev_lidar_depth_workspace": (C.c_size_t, [C.c_int, C.c_int]),
     "ssbev_lidar_depth_map": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "ssbev_occ_depth_workspace": (C.c_size_t, [C.c_int, C.c_int]),
+    "ssbev_occ_depth_map": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P,
+                                      C.c_size_t, _P]),
+    "ssbev_label_map_downsample": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "ssbev_dwconv2d_fwd": (C.c_int, [_P, _P, _P, C.POINTER(DwDims), _P]),
     "ssbev_dwconv2d_bwd_data": (C.c_int, [_P, _P, _P, C.POINTER(DwDims), _P]),
     "ssbev_dwconv2d_bwd_weight_workspace": (C.c_size_t, [C.POINTER(DwDims)]),

@@ -2644,6 +2644,169 @@ def bev_label_transform(labels_u8, coeffs, flip_dx, flip_dy, inplace=True, fill=
 
 
 # -------------------------------------------------------------------------------------------------
+# Occupancy -> depth map and image-view label map (csrc/occ_depth.hip)
+# -------------------------------------------------------------------------------------------------
+SSBEV_OCC_DEPTH = os.environ.get("SSBEV_OCC_DEPTH", "1") != "0"   # CreateDepthFromOccupancy on the GPU (0 = the tensor form on the host, then one upload)
+SEG_OCCLUDERS = ("reference", "occupied")
+_OCC_TABLES = {}                                                  # (range, grid, device) -> the three centre tables, made once
+
+
+def occ_voxel_tables(point_cloud_range, grid_size, device="cpu"):
+    """The voxel centres per axis as ``CreateDepthFromOccupancy.init_voxel_coordinates`` makes them (occ_to_depth.py:32-38: the
+    same ``torch.arange`` over float64 bounds, so the fp32 centres carry its bits): one fp32 tensor [X + Y + Z] on ``device``."""
+    grid = tuple(int(v) for v in grid_size)
+    key = (tuple(float(v) for v in point_cloud_range), grid, str(device))
+    t = _OCC_TABLES.get(key)
+    if t is None:
+        r = np.array(key[0], dtype=np.float64)
+        size = (r[3:] - r[:3]) / np.array(grid)
+        lo = r[:3] + size / 2
+        tabs = [torch.arange(lo[i], r[3 + i], size[i]) for i in range(3)]
+        if tuple(int(a.numel()) for a in tabs) != grid:
+            raise ValueError(f"occ_voxel_tables: torch.arange gives {[int(a.numel()) for a in tabs]} centres for the grid {grid} "
+                             f"(the reference's .view(X, 1, 1) fails the same way)")
+        if len(_OCC_TABLES) >= 16:
+            _OCC_TABLES.clear()
+        t = _OCC_TABLES[key] = torch.cat(tabs).float().contiguous().to(device)
+    return t
+
+
+def occ_camera(view):
+    """The 46 camera floats of ``ssbev_occ_depth_map`` from one view of ``img_inputs`` (slots 1..6: rots, trans, intrins,
+    post_rots, post_trans, bda), on the host: ``inv(bda)[:3]`` as 3x4 | ``inv(rots)`` | trans | intrins 4x4 | ``post_rots[:2,:2]``
+    | ``post_trans[:2]``, both inverses by ``torch.inverse`` in fp32 as the reference takes them (occ_to_depth.py:45, :51).
+    Returns (cam [46] fp32 CPU, n = 3 or 4, the size of the BEV matrix)."""
+    def host(t):
+        return torch.as_tensor(t).detach().float().cpu()
+    rots, trans, intrins, post_rots, post_trans, bda = (host(t) for t in view[1:7])
+    n = int(bda.shape[-1])
+    if n not in (3, 4) or bda.numel() != n * n:
+        raise ValueError(f"occupancy_depth_map: one 3x3 or 4x4 BEV matrix expected in slot 6, got {tuple(bda.shape)}")
+    inv_bda = torch.zeros(3, 4)
+    inv_bda[:, :n] = torch.inverse(bda.reshape(n, n))[:3]
+    cam = torch.cat([inv_bda.reshape(-1), torch.inverse(rots.reshape(3, 3)).reshape(-1), trans.reshape(-1)[:3],
+                     intrins.reshape(4, 4).reshape(-1), post_rots.reshape(3, 3)[:2, :2].reshape(-1),
+                     post_trans.reshape(-1)[:2]]).contiguous()
+    assert cam.numel() == 46
+    return cam, n
+
+
+def _occ_depth_tensor(lab, tabs, cam, n, occupied_only, H, W):
+    """``ssbev_occ_depth_map`` in elementwise tensor operations on the host, one rounding per operation in the kernel's order,
+    the nearest voxel per pixel by the same 64-bit key (depth bits << 32 | flat index) under ``amin``."""
+    X, Y, Z = (int(v) for v in lab.shape)
+    N = X * Y * Z
+    px = tabs[:X].view(X, 1, 1).expand(X, Y, Z).reshape(-1)
+    py = tabs[X:X + Y].view(1, Y, 1).expand(X, Y, Z).reshape(-1)
+    pz = tabs[X + Y:].view(1, 1, Z).expand(X, Y, Z).reshape(-1)
+    A, R, t, K, pr, pt = cam[0:12], cam[12:21], cam[21:24], cam[24:40], cam[40:44], cam[44:46]
+    l3 = [(A[4 * i] * px + A[4 * i + 1] * py) + A[4 * i + 2] * pz for i in range(3)]
+    if n == 4:
+        l3 = [l3[i] + A[4 * i + 3] for i in range(3)]
+    x, y, z = (l3[i] - t[i] for i in range(3))
+    cx, cy, cz = ((R[3 * i] * x + R[3 * i + 1] * y) + R[3 * i + 2] * z for i in range(3))
+    qx, qy, d = (((K[4 * i] * cx + K[4 * i + 1] * cy) + K[4 * i + 2] * cz) + K[4 * i + 3] for i in range(3))
+    u0, v0 = qx / d, qy / d
+    u = (pr[0] * u0 + pr[1] * v0) + pt[0]
+    v = (pr[2] * u0 + pr[3] * v0) + pt[1]
+    ok = (u >= 0) & (v >= 0) & (u <= W - 1) & (v <= H - 1) & (d > 0)
+    flat = lab.reshape(-1)
+    occupied = (flat != 0) & (flat != 255)
+    idx = torch.arange(N, dtype=torch.int64)
+    none = torch.iinfo(torch.int64).max
+
+    def nearest(mask):
+        pix = torch.round(v[mask]).long() * W + torch.round(u[mask]).long()
+        key = (d[mask].contiguous().view(torch.int32).long() << 32) | idx[mask]
+        return torch.full((H * W,), none, dtype=torch.int64).scatter_reduce_(0, pix, key, "amin")
+
+    zd = nearest(ok & occupied)
+    zs = zd if occupied_only else nearest(ok)
+    depth = torch.where(zd != none, (zd >> 32).to(torch.int32).view(torch.float32), torch.zeros(()))
+    hit = zs != none
+    seg = torch.where(hit, flat[torch.where(hit, zs & 0xFFFFFFFF, torch.zeros_like(zs))].float(), torch.full((), 255.0))
+    return depth.view(H, W), seg.view(H, W)
+
+
+def label_map_downsample(seg, downscale=16):
+    """``CreateDepthFromOccupancy._downsample_label`` (occ_to_depth.py:67-93): a label map [H,W] (float holding 0..255; any other
+    value counts as 255) -> float32 [H // ds, W // ds], trailing rows and columns dropped.  A patch with more than ``0.95 ds^2``
+    pixels 0 or 255 (compared in fp32, as the reference's tensor-against-float comparison does) becomes 0 when the zeros outnumber
+    the 255s and 255 otherwise (a tie included); any other patch takes its most frequent label in 1..254, the LOWEST on a tie --
+    what ``torch.mode`` returns on the CPU.  CUDA maps run ``ssbev_label_map_downsample``; CPU maps the same rule in tensor ops."""
+    ds = int(downscale)
+    seg = torch.as_tensor(seg)
+    if seg.dim() != 2 or not 1 <= ds <= 256:
+        raise ValueError(f"label_map_downsample: a [H,W] map and a downscale in 1..256 expected, got {tuple(seg.shape)}, {downscale}")
+    H, W = (int(v) for v in seg.shape)
+    oh, ow = H // ds, W // ds
+    empty_t = float(torch.tensor(0.95 * ds * ds, dtype=torch.float32))
+    if seg.is_cuda:
+        lib = capi.load()
+        src = seg.float().contiguous()
+        out = torch.empty(oh, ow, dtype=torch.float32, device=seg.device)
+        if H and W:
+            capi.check(lib.ssbev_label_map_downsample(capi.ptr(src), capi.ptr(out), H, W, ds, empty_t, capi.stream()),
+                       "ssbev_label_map_downsample")
+        return out
+    if oh == 0 or ow == 0:
+        return torch.empty(oh, ow, dtype=torch.float32)
+    v = seg.float()[:oh * ds, :ow * ds]
+    lab = torch.where((v >= 0) & (v <= 255), v, torch.full((), 255.0)).long()
+    patches = lab.reshape(oh, ds, ow, ds).permute(0, 2, 1, 3).reshape(-1, ds * ds)
+    hist = torch.zeros(patches.shape[0], 256, dtype=torch.int64).scatter_add_(1, patches, torch.ones_like(patches))
+    z0, z255 = hist[:, 0], hist[:, 255]
+    empty = (z0 + z255).float() > empty_t
+    ids = torch.arange(1, 255)
+    cls = ids[(hist[:, 1:255] * 256 + (255 - ids)).argmax(1)]                     # the larger count, then the lower id
+    out = torch.where(empty, torch.where(z0 > z255, torch.zeros_like(cls), torch.full_like(cls, 255)), cls)
+    return out.float().view(oh, ow)
+
+
+def occupancy_depth_map(labels, view, point_cloud_range, seg_occluders="reference", downsample=False, downscale=16):
+    """The loader step ``CreateDepthFromOccupancy`` of one view (occ_to_depth.py:95-149): voxel labels [X,Y,Z] (0 = empty, 255 =
+    ignored) and one view of ``img_inputs`` -> (depth float32 [H,W]: the depth of the nearest voxel centre labelled 1..254 per
+    pixel, 0 where none; seg float32 [H,W], or [H // ds, W // ds] with ``downsample``: the label of the nearest centre, 255 where
+    none).  The image size is that of ``view[0]``; the grid is the labels' shape.
+    ``seg_occluders="reference"``: as upstream, EVERY in-view centre competes for the label map, empty and ignored voxels
+    included, so whatever voxel lies in front of a surface along a pixel's ray takes that pixel with its own label.
+    ``"occupied"``: only labels 1..254 compete; a pixel shows the first occupied voxel, on the mask the depth map uses.
+    Exact fp32 depth ties go to the lowest flat voxel index (upstream leaves them open).
+    CUDA labels run ``ssbev_occ_depth_map`` (+ ``ssbev_label_map_downsample``); CPU labels the same fp32 arithmetic in tensor
+    ops; with ``SSBEV_OCC_DEPTH`` off CUDA labels take the tensor form on the host and the maps are uploaded once."""
+    if seg_occluders not in SEG_OCCLUDERS:
+        raise ValueError(f"occupancy_depth_map: seg_occluders must be one of {SEG_OCCLUDERS}, got {seg_occluders!r}")
+    labels = torch.as_tensor(labels)
+    if labels.dim() != 3 or labels.dtype.is_floating_point:
+        raise ValueError(f"occupancy_depth_map: integer labels [X,Y,Z] expected, got {labels.dtype} {tuple(labels.shape)}")
+    X, Y, Z = (int(v) for v in labels.shape)
+    H, W = (int(v) for v in view[0].shape[-2:])
+    if min(X, Y, Z, H, W) < 1:
+        raise ValueError(f"occupancy_depth_map: empty grid {(X, Y, Z)} or image {(H, W)}")
+    cam, n = occ_camera(view)
+    occupied_only = seg_occluders == "occupied"
+    dev = labels.device
+    if labels.is_cuda and SSBEV_OCC_DEPTH:
+        lib = capi.load()
+        lab = labels.to(torch.uint8).contiguous()
+        tabs = occ_voxel_tables(point_cloud_range, (X, Y, Z), dev)
+        depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+        seg = torch.empty(H, W, dtype=torch.float32, device=dev)
+        ws = _ws(lib.ssbev_occ_depth_workspace(H, W), dev)
+        base = tabs.data_ptr()
+        capi.check(lib.ssbev_occ_depth_map(capi.ptr(lab), X, Y, Z, C.c_void_p(base), C.c_void_p(base + 4 * X),
+                                           C.c_void_p(base + 4 * (X + Y)), C.c_void_p(cam.data_ptr()), n, int(occupied_only),
+                                           capi.ptr(depth), capi.ptr(seg), H, W, capi.ptr(ws), ws.numel(), capi.stream()),
+                   "ssbev_occ_depth_map")
+        return depth, (label_map_downsample(seg, downscale) if downsample else seg)
+    tabs = occ_voxel_tables(point_cloud_range, (X, Y, Z))
+    depth, seg = _occ_depth_tensor(labels.cpu().to(torch.uint8), tabs, cam, n, occupied_only, H, W)
+    if downsample:
+        seg = label_map_downsample(seg, downscale)
+    return depth.to(dev), seg.to(dev)
+
+
+# -------------------------------------------------------------------------------------------------
 # 3-D context relation prior (csrc/crp.hip): label down-sampling, relation matrix, relation loss, relation gather
 # -------------------------------------------------------------------------------------------------
 CRP = os.environ.get("SSBEV_CRP", "1") != "0"                # fused relation loss and gather (0 = the tensor forms: sigmoid, bmm, cat, BCEWithLogits)

@@ -160,6 +160,61 @@ class CreateDepthFromLiDAR:
 
 
 @PIPELINES.register_module()
+class CreateDepthFromOccupancy:
+    """Pipeline step ``CreateDepthFromOccupancy`` (datasets/pipelines/occ_to_depth.py:15-153), the producer of image-view
+    supervision that needs nothing but ``results['gt_occ']``: every voxel centre is projected into a view, the nearest centre
+    labelled 1..254 per pixel gives the depth map (slot 7 of ``img_inputs[k]``, what the depth loss reads) and the nearest centre
+    gives the label map ``img_seg`` (what ``loss_imgseg`` reads); ``downsample=True`` pools the label map per 16 x 16 patch
+    (``functional.label_map_downsample``).  ``gt_occ`` may be numpy, a CPU tensor or a CUDA tensor; the step runs where it lives
+    (``device=None``) or on ``device``; on the GPU it is ``functional.occupancy_depth_map``'s kernels.  Placed after
+    ``CreateDepthFromLiDAR`` it replaces that step's depth and label maps (upstream's comment at :142 says the same).
+
+    The one departure from upstream's text: the depth map IS written into slot 7.  Upstream unpacks the view into nine names
+    (:143) where this model's loader makes ten-element views (loading_semkitti.py:399), and its write-back (:144) assigns into a
+    temporary list, so the depth map it computes is dropped even where the unpack passes.
+
+    ``seg_occluders``: ``"reference"`` keeps upstream's label map, where every in-view voxel competes -- an empty (0) or
+    ignored (255) voxel in front of a surface takes the pixel (:133); ``"occupied"`` lets only labels 1..254 compete, the mask the
+    depth map uses.  Exact depth ties go to the lowest voxel index (upstream leaves them open).
+    ``views``: ``"left"`` is upstream's choice (``img_inputs[0]``, :107): the left view's slot is written, ``img_seg`` and
+    ``img_seg_left`` both hold its label map.  ``"both"`` also fills the right view's slot; ``img_seg`` is then the RIGHT view's
+    map and ``img_seg_left`` the left one's, the convention of ``CreateDepthFromLiDAR``.
+    A 4 x 4 BEV matrix (``LoadSemKittiAnnotation(apply_bda=True)``) is inverted as it is and applied to ``[p; 1]``."""
+
+    VIEWS = ("left", "both")
+
+    def __init__(self, point_cloud_range, grid_size, downsample=False, seg_occluders="reference", views="left", device=None):
+        from . import functional as F
+        if seg_occluders not in F.SEG_OCCLUDERS:
+            raise ValueError(f"CreateDepthFromOccupancy: seg_occluders must be one of {F.SEG_OCCLUDERS}, got {seg_occluders!r}")
+        if views not in self.VIEWS:
+            raise ValueError(f"CreateDepthFromOccupancy: views must be one of {self.VIEWS}, got {views!r}")
+        self.grid_size = np.array(grid_size)
+        self.point_cloud_range = np.array(point_cloud_range, dtype=np.float64)
+        self.voxel_size = (self.point_cloud_range[3:] - self.point_cloud_range[:3]) / self.grid_size
+        self.downsample, self.seg_occluders, self.views, self.device = bool(downsample), seg_occluders, views, device
+        F.occ_voxel_tables(self.point_cloud_range, self.grid_size)              # a range / grid pair torch.arange cannot serve fails here
+
+    def __call__(self, results):
+        from . import functional as F
+        labels = torch.as_tensor(results["gt_occ"])
+        if tuple(labels.shape) != tuple(int(v) for v in self.grid_size):
+            raise ValueError(f"CreateDepthFromOccupancy: gt_occ {tuple(labels.shape)} is not the grid {tuple(self.grid_size)}")
+        lab = labels if self.device is None else labels.to(self.device)
+        inputs = list(results["img_inputs"])
+        for k in range(2 if self.views == "both" else 1):
+            depth, img_seg = F.occupancy_depth_map(lab, inputs[k], self.point_cloud_range, self.seg_occluders, self.downsample)
+            view = list(inputs[k])
+            view[7] = depth.unsqueeze(0)
+            inputs[k] = view
+            results["img_seg"] = img_seg
+            if k == 0:
+                results["img_seg_left"] = img_seg
+        results["img_inputs"] = inputs
+        return results
+
+
+@PIPELINES.register_module()
 class CreateRelationLabels:
     """Pipeline step ``CreateRelationLabels`` (datasets/pipelines/voxel_labels.py:65-265), the part the upstream runs: the
     frustum of every voxel of ``results['gt_occ']`` and the class counts per frustum, the inputs of the head's frustum-proportion
