@@ -285,6 +285,28 @@ int ssbev_conv_bwd_data(const float* gy, const float* w_packed_t, float* gx,
 size_t ssbev_conv_bwd_weight_workspace(const ssbev_conv_dims* d);
 int ssbev_conv_bwd_weight(const float* x, const float* gy, float* gw, const ssbev_conv_dims* d,
                           void* ws, size_t ws_bytes, ssbev_stream_t stream);
+/* Host-side plan query of the weight gradient (since ssbev_version() 123; no device work): the kind ssbev_conv_bwd_weight takes for these dims, the partial
+ * slabs [nchunks][taps][Cq][Cp] it leaves at the start of the workspace, how they are folded, and the launch numbers of that kind,
+ * all from the functions the launch itself reads.  Only the group of the reported kind is filled in, every other field is 0
+ * (kind 0, bf16 storage: `kind` and `workspace` only; ssbev_conv_bf16_plan_query describes that launch).  SSBEV_EINVAL for a
+ * NULL argument or dims no entry point takes. */
+typedef struct {
+  int kind;                       /* 0 bf16 storage, 1 thin side (wgrad_thinside_kernel), 2 thin (wgrad_thin_kernel), 3 pointwise
+                                   * (wgrad_1x1_kernel), 4 F(2,3) x F(2,3) ring walk (wgrad_tapdh_kernel), 5 LDS-staged
+                                   * (wgrad_lds_kernel), 6 channels-first (wgrad_cf_kernel), 7 direct (wgrad_kernel) */
+  int nchunks, taps, Cq, Cp;      /* slabs handed to the fold (5: workgroup chunks x ksplit), taps per slab (4: the 48 of the
+                                   * transform domain), Q (tap side) and P (coarse-grid side) channels */
+  int two_stage, nsl, per;        /* kinds 2 .. 7: wgrad_reduce_stage_kernel runs first, over nsl slices of `per` slabs (the last
+                                   * slice may be shorter); 0 0 0 when it does not */
+  int final;                      /* kinds 2 .. 7: 0 = wgrad_reduce_kernel, 1 = wgrad_reduce_tiled_kernel (1: its own fold, 0) */
+  int cfg, Wseg, RG, nseg, gpc, nranges, ksplit;   /* 5: <MQB, MPB, KDB, KSPLIT, S> number, w-segment, P rows per step, segments,
+                                   * row groups per chunk, chunk ranges, k split; 2 and 4: nseg and gpc of their row walks */
+  int instance;                   /* 5: 0 plain, 1 F(2,3) along h, 2 the same with the unrolled NKS = 4 k-step count */
+  int MQ, MP, TH, TW, chunk;      /* 3: wgrad_1x1_kernel<MQ, MP>, voxels per wave chunk; 6, 7: <MQ, MP, TH, TW>, voxels per chunk */
+  int rows_per_wave, nt;          /* 1: rows per wave chunk, thin-side channel count */
+  size_t workspace;               /* bytes, what ssbev_conv_bwd_weight_workspace returns */
+} ssbev_conv_wgrad_plan;
+int ssbev_conv_wgrad_plan_query(const ssbev_conv_dims* d, ssbev_conv_wgrad_plan* out);
 
 /* Batched plain products of the bf16 storage mode (round 5): C[b][m][n] = sum_k A[b][m][k] B[b][k][n], A and (out_fp32 = 0) C
  * bf16 bit patterns, fp32 accumulation on v_mfma_f32_32x32x16_bf16 -- the Winograd frequency products (functional._WinoConv:

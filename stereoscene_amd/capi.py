@@ -163,6 +163,12 @@ class ConvBf16Plan(C.Structure):
         [("grid", C.c_int64), ("workspace", C.c_size_t)]
 
 
+class ConvWgradPlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("kind", "nchunks", "taps", "Cq", "Cp", "two_stage", "nsl", "per", "final", "cfg", "Wseg", "RG",
+                                       "nseg", "gpc", "nranges", "ksplit", "instance", "MQ", "MP", "TH", "TW", "chunk",
+                                       "rows_per_wave", "nt")] + [("workspace", C.c_size_t)]
+
+
 class JitterParams(C.Structure):
     _fields_ = [("flags", C.c_int), ("mode", C.c_int), ("delta", C.c_float), ("alpha", C.c_float), ("saturation", C.c_float),
                 ("hue", C.c_float), ("perm", C.c_int * 3)]
@@ -215,6 +221,7 @@ SIGNATURES = {
     "ssbev_conv_bwd_weight_bf16": (C.c_int, [_P, _P, _P, C.POINTER(ConvDims), _P, C.c_size_t, _P]),
     "ssbev_conv_bwd_weight_workspace": (C.c_size_t, [C.POINTER(ConvDims)]),
     "ssbev_conv_bwd_weight": (C.c_int, [_P, _P, _P, C.POINTER(ConvDims), _P, C.c_size_t, _P]),
+    "ssbev_conv_wgrad_plan_query": (C.c_int, [C.POINTER(ConvDims), C.POINTER(ConvWgradPlan)]),
     "ssbev_gemm16_packed_elems": (C.c_size_t, [C.POINTER(Gemm16Dims)]),
     "ssbev_gemm16_pack": (C.c_int, [_P, _P, C.POINTER(Gemm16Dims), _P]),
     "ssbev_gemm16_nn": (C.c_int, [_P, _P, _P, C.POINTER(Gemm16Dims), _P]),

@@ -659,21 +659,37 @@ wgrad_reduce_stage_kernel(float* __restrict__ ws, int nchunks, int per, long tot
   *base = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
 }
 
+// Which of the kernels above fold `nchunks` partial slabs: the stage kernel first (nsl slices of `per` slabs, the last one
+// shorter) or not, then the tiled or the plain kernel.  launch_wgrad_reduce and ssbev_conv_wgrad_plan_query both read this.
+struct WgradReducePlan { bool two_stage; int nsl, per; bool tiled; };
+
+WgradReducePlan plan_wgrad_reduce(int nchunks, int taps, int Cq, int Cp) {
+  WgradReducePlan r{false, 0, 0, false};
+  const long total = (long)taps * Cq * Cp;
+  static const int two_stage = ssbev_tune("SSBEV_WGRAD_REDUCE2") ? atoi(ssbev_tune("SSBEV_WGRAD_REDUCE2")) : 1;
+  if (two_stage && nchunks >= 64 && total % 4 == 0) {
+    const long bx = cdiv(total / 4, 256);
+    const int nsl = (int)std::min<long>(std::max<long>(cdiv(2048, bx), 1), nchunks / 8);
+    r.two_stage = true;
+    r.per = cdiv(nchunks, nsl);
+    r.nsl = cdiv(nchunks, r.per);
+  }
+  r.tiled = taps <= 32 && (long)cdiv(Cp, 32) * cdiv(Cq, 8) >= 128;
+  return r;
+}
+
 void launch_wgrad_reduce(float* partial, float* gw, int nchunks, int taps, int Cq, int Cp, hipStream_t st) {
   const long total = (long)taps * Cq * Cp;
   long cstride = total;
-  static const int two_stage = ssbev_tune("SSBEV_WGRAD_REDUCE2") ? atoi(ssbev_tune("SSBEV_WGRAD_REDUCE2")) : 1;
-  if (two_stage && nchunks >= 64 && total % 4 == 0) {
+  const WgradReducePlan r = plan_wgrad_reduce(nchunks, taps, Cq, Cp);
+  if (r.two_stage) {
     const long total4 = total / 4, bx = cdiv(total4, 256);
-    int nsl = (int)std::min<long>(std::max<long>(cdiv(2048, bx), 1), nchunks / 8);
-    const int per = cdiv(nchunks, nsl);
-    nsl = cdiv(nchunks, per);
-    hipLaunchKernelGGL(wgrad_reduce_stage_kernel, dim3((unsigned)bx, (unsigned)nsl), dim3(256), 0, st, partial, nchunks, per,
+    hipLaunchKernelGGL(wgrad_reduce_stage_kernel, dim3((unsigned)bx, (unsigned)r.nsl), dim3(256), 0, st, partial, nchunks, r.per,
                        total4);
-    nchunks = nsl;
-    cstride = (long)per * total;
+    nchunks = r.nsl;
+    cstride = (long)r.per * total;
   }
-  if (taps <= 32 && (long)cdiv(Cp, 32) * cdiv(Cq, 8) >= 128) {
+  if (r.tiled) {
     hipLaunchKernelGGL(wgrad_reduce_tiled_kernel, dim3(cdiv(Cp, 32), cdiv(Cq, 8)), dim3(256),
                        (size_t)32 * (8 * taps + 1) * sizeof(float), st, partial, gw, nchunks, taps, Cq, Cp, total, cstride);
   } else {
@@ -1966,16 +1982,23 @@ int launch_wgrad_lds(const float* P, const float* Q, float* ws, const WgradLdsPl
   return SSBEV_OK;
 }
 
+// The cfg 1 (<= 32 x 32 channels) instance: 1 = F(2,3) along h over row pairs when the step holds whole pairs, 2 = the same with
+// the unrolled NKS = 4 k-step count, 0 = plain (tile_hint 6: plain; 5: run-time k-step count).  The other cfgs have one instance, 0.
+int wgrad_lds_instance(const WgradLdsPlan& p, int tile_hint) {
+  if (p.cfg != 1 || p.g.RG % 2 != 0 || tile_hint == 6) return 0;
+  return p.g.Wseg == 32 && tile_hint != 5 ? 2 : 1;
+}
+
 int run_wgrad_lds(const float* x, const float* gy, float* ws, const ssbev_conv_dims* d, const WgradLdsPlan& p,
                   hipStream_t st) {
   const float* P = d->transposed ? x : gy;
   const float* Q = d->transposed ? gy : x;
   switch (p.cfg) {
     case 0: return launch_wgrad_lds<2, 2, 1, 1, 1>(P, Q, ws, p, st);
-    case 1:   // <= 32 x 32 channels: F(2,3) along h over row pairs when the step holds whole pairs (tile_hint 6: plain; 5: run-time k-step count instead of the unrolled NKS = 4 instance)
-      if (p.g.RG % 2 == 0 && d->tile_hint != 6) {
-        if (p.g.Wseg == 32 && d->tile_hint != 5) return launch_wgrad_lds<1, 1, 1, 4, 1, true, 4>(P, Q, ws, p, st);
-        return launch_wgrad_lds<1, 1, 1, 4, 1, true>(P, Q, ws, p, st);
+    case 1:
+      switch (wgrad_lds_instance(p, d->tile_hint)) {
+        case 2: return launch_wgrad_lds<1, 1, 1, 4, 1, true, 4>(P, Q, ws, p, st);
+        case 1: return launch_wgrad_lds<1, 1, 1, 4, 1, true>(P, Q, ws, p, st);
       }
       return launch_wgrad_lds<1, 1, 1, 4, 1>(P, Q, ws, p, st);
     case 2: return launch_wgrad_lds<1, 2, 1, 2, 2>(P, Q, ws, p, st);
@@ -4391,6 +4414,59 @@ int ssbev_conv_chunk_groups(const ssbev_conv_dims* d, int mode) {
 int ssbev_conv_bf16_plan_query(const ssbev_conv_dims* d, int mode, ssbev_conv_bf16_plan* out) {
   if (!conv_dims_ok(d) || !ssbev_bf16::storage_mode(d)) return SSBEV_EINVAL;
   return ssbev_bf16::plan_query(d, mode, out);
+}
+
+// ssbev_conv_wgrad_plan_query: select_wgrad's own answer, and the fold plan launch_wgrad_reduce will read for it.  No device call.
+int ssbev_conv_wgrad_plan_query(const ssbev_conv_dims* d, ssbev_conv_wgrad_plan* out) {
+  if (!conv_dims_ok(d) || !out) return SSBEV_EINVAL;
+  *out = ssbev_conv_wgrad_plan{};
+  const WgradPlan p = select_wgrad(d);
+  out->kind = (int)p.kind;
+  out->workspace = p.ws_bytes;
+  bool shared_fold = true;
+  switch (p.kind) {
+    case WgradKind::Bf16Storage: return SSBEV_OK;            // (ssbev_conv_bf16_plan_query, mode 2, describes that launch)
+    case WgradKind::ThinSide: {                              // wgrad_thinside_reduce_kernel is its own fold
+      const ssbev_thin::ThinWgradPlan t = ssbev_thin::wgrad_plan(d);
+      out->rows_per_wave = t.rows_per_wave; out->nchunks = t.nchunks; out->nt = t.nt;
+      out->taps = 27; out->Cq = d->Cin; out->Cp = d->Cout;
+      shared_fold = false;
+      break;
+    }
+    case WgradKind::Thin:
+      out->nchunks = p.thin.nchunks; out->taps = 27; out->Cq = d->Cin; out->Cp = d->Cout;
+      out->gpc = p.thin.g.gpc; out->nseg = p.thin.g.nseg;
+      break;
+    case WgradKind::Pointwise:
+      out->nchunks = p.p1.nchunks; out->taps = 1; out->Cq = p.p1.Cq; out->Cp = p.p1.Cp;
+      out->MQ = p.p1.MQ; out->MP = p.p1.MP; out->chunk = p.p1.chunk;
+      break;
+    case WgradKind::Dh:
+      out->nchunks = p.dh.nchunks; out->taps = 48; out->Cq = p.dh.g.Cq; out->Cp = p.dh.g.Cp;
+      out->gpc = p.dh.g.gpc; out->nseg = p.dh.g.nseg;
+      break;
+    case WgradKind::Lds: {
+      const WgradLdsGeom& g = p.lds.g;
+      out->nchunks = p.lds.nchunks * p.lds.ksplit; out->taps = d->kd * 9; out->Cq = g.Cq; out->Cp = g.Cp;
+      out->cfg = p.lds.cfg; out->Wseg = g.Wseg; out->RG = g.RG; out->nseg = g.nseg; out->gpc = g.gpc; out->nranges = g.nranges;
+      out->ksplit = p.lds.ksplit; out->instance = wgrad_lds_instance(p.lds, d->tile_hint);
+      break;
+    }
+    case WgradKind::ChannelsFirst:
+      out->nchunks = p.cf.nchunks; out->taps = p.cf.kd * p.cf.kh * p.cf.kw; out->Cq = p.cf.Cq; out->Cp = p.cf.Cp;
+      out->MQ = p.cfg.MQ; out->MP = p.cfg.MP; out->TH = p.cfg.TH; out->TW = p.cfg.TW; out->chunk = p.cf.chunk;
+      break;
+    case WgradKind::Direct:
+      out->nchunks = p.direct.nchunks; out->taps = p.direct.kd * p.direct.kh * p.direct.kw;
+      out->Cq = p.direct.Cq; out->Cp = p.direct.Cp;
+      out->MQ = p.cfg.MQ; out->MP = p.cfg.MP; out->TH = p.cfg.TH; out->TW = p.cfg.TW; out->chunk = p.direct.chunk;
+      break;
+  }
+  if (shared_fold) {
+    const WgradReducePlan r = plan_wgrad_reduce(out->nchunks, out->taps, out->Cq, out->Cp);
+    out->two_stage = r.two_stage; out->nsl = r.nsl; out->per = r.per; out->final = r.tiled;
+  }
+  return SSBEV_OK;
 }
 
 size_t ssbev_conv_packed_weight_elems(const ssbev_conv_dims* d) {

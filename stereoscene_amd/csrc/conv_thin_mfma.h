@@ -24,6 +24,9 @@ int thinout_launch(const float* x, const float* wp, const float* bias, float* y,
 // weight gradient of both kinds (32 <-> 1 / 2 / 4 channels, unpadded tensors)
 bool wgrad_applicable(const ssbev_conv_dims* d);
 size_t wgrad_workspace(const ssbev_conv_dims* d);
+// rows per wave chunk, chunks (= workspace slabs of mt 32 x 32 tiles), thin-side channel count nt, which side is thin
+struct ThinWgradPlan { int rows_per_wave, nchunks, nt, mt; bool thin_out; };
+ThinWgradPlan wgrad_plan(const ssbev_conv_dims* d);
 int wgrad_launch(const float* x, const float* gy, float* gw, const ssbev_conv_dims* d, void* ws, size_t ws_bytes, hipStream_t st);
 
 }  // namespace ssbev_thin

@@ -410,12 +410,23 @@ int thinout_launch(const float* x, const float* wp, const float* bias, float* y,
   return ssbev_launch_status();
 }
 
-static ThinWgGeom make_wg_geom(const ssbev_conv_dims* d) {
+// The one plan of the thin-side weight gradient: the launch geometry, the workspace and ssbev_conv_wgrad_plan_query all read it.
+ThinWgradPlan wgrad_plan(const ssbev_conv_dims* d) {
+  ThinWgradPlan p;
+  const int nrows = d->B * d->Do * d->Ho;
+  p.rows_per_wave = std::max(1, (nrows + 4607) / 4608);
+  p.nchunks = (nrows + p.rows_per_wave - 1) / p.rows_per_wave;
+  p.thin_out = d->Cin == 32 && d->Cout != 32;
+  p.nt = p.thin_out ? d->Cout : d->Cin;
+  p.mt = (27 * p.nt + 31) / 32;
+  return p;
+}
+
+static ThinWgGeom make_wg_geom(const ssbev_conv_dims* d, const ThinWgradPlan& p) {
   ThinWgGeom g;
   g.B = d->B; g.D = d->Do; g.H = d->Ho; g.W = d->Wo;
-  const int nrows = g.B * g.D * g.H;
-  g.rows_per_wave = std::max(1, (nrows + 4607) / 4608);
-  g.nchunks = (nrows + g.rows_per_wave - 1) / g.rows_per_wave;
+  g.rows_per_wave = p.rows_per_wave;
+  g.nchunks = p.nchunks;
   return g;
 }
 
@@ -426,9 +437,8 @@ bool wgrad_applicable(const ssbev_conv_dims* d) {
 }
 
 size_t wgrad_workspace(const ssbev_conv_dims* d) {
-  const ThinWgGeom g = make_wg_geom(d);
-  const int nt = d->Cin == 32 ? d->Cout : d->Cin, mt = (27 * nt + 31) / 32;
-  return (size_t)g.nchunks * mt * 1024 * sizeof(float);
+  const ThinWgradPlan p = wgrad_plan(d);
+  return (size_t)p.nchunks * p.mt * 1024 * sizeof(float);
 }
 
 template <int NT, int SGN>
@@ -438,9 +448,10 @@ static void wgrad_run(const float* wide, const float* thin, float* ws, const Thi
 
 int wgrad_launch(const float* x, const float* gy, float* gw, const ssbev_conv_dims* d, void* ws, size_t ws_bytes, hipStream_t st) {
   if (!ws || ws_bytes < wgrad_workspace(d)) return SSBEV_EWORKSPACE;
-  const ThinWgGeom g = make_wg_geom(d);
-  const bool thin_out = d->Cin == 32 && d->Cout != 32;
-  const int nt = thin_out ? d->Cout : d->Cin, mt = (27 * nt + 31) / 32;
+  const ThinWgradPlan p = wgrad_plan(d);
+  const ThinWgGeom g = make_wg_geom(d, p);
+  const bool thin_out = p.thin_out;
+  const int nt = p.nt, mt = p.mt;
   float* wsf = static_cast<float*>(ws);
   if (thin_out) {
     if (nt == 1) wgrad_run<1, -1>(x, gy, wsf, g, st);

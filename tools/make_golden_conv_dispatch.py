@@ -7,10 +7,8 @@ so it is recorded from the library of the commit BEFORE a dispatch change and ne
 is therefore mandatory and `--commit` names the commit that library was built from (stored in the file).
 
 Rows ("cols" names the fields): the 26 ints of ssbev_conv_dims, ssbev_conv_kernel_class and ssbev_conv_chunk_groups for modes
-0 / 1 / 2, ssbev_conv_packed_weight_elems, ssbev_conv_bwd_weight_workspace and the weight-gradient kind as a label.  The label is
-derived without looking into the library's ladder: storage mode and thin-side class from the public queries, the two simple shape
-predicates restated here, the ring-walk kind from its chunk query, and the LDS kind from the tile_hint 7 A/B pair (hint 7 keeps
-the channel-major / direct kernels, so a workspace that changes under it belonged to the LDS kernel).
+0 / 1 / 2, ssbev_conv_packed_weight_elems, ssbev_conv_bwd_weight_workspace and the weight-gradient kind as a label: the `kind` of
+ssbev_conv_wgrad_plan_query (libraries older than ssbev_version() 123 do not have it).
 "igemm_off" holds the rows whose class is 11 or 0 once more under SSBEV_IGEMM=0 (recorded by a child process; this process sets
 no SSBEV_* variable), "retcodes" the SSBEV_EINVAL answers of the fp32 entry points that return before any device call."""
 import argparse
@@ -126,33 +124,14 @@ def open_lib(path):
     return lib
 
 
-def _same_grid(d):
-    return (d.Di, d.Hi, d.Wi) == (d.Do, d.Ho, d.Wo)
-
-
 def wgrad_kind(lib, d):
-    if d.precision >= 2:
-        return "bf16"
-    if lib.ssbev_conv_kernel_class(C.byref(d), 2) == 6:
-        return "thinside"
-    k, s, p, dl = (d.kd, d.kh, d.kw), (d.sd, d.sh, d.sw), (d.pd, d.ph, d.pw), (d.dd, d.dh, d.dw)
-    if (not d.transposed and k == (3, 3, 3) and s == (1, 1, 1) and p == (1, 1, 1) and dl == (1, 1, 1) and _same_grid(d)
-            and d.tile_hint != 7 and 16 <= d.Cin <= 32 and d.Cin % 4 == 0 and d.Cout <= 4
-            and (d.tile_hint == 9 or d.B * d.Do * d.Ho * ((d.Wo + 31) // 32) >= 1024 * 16)):
-        return "thin"
-    if k == (1, 1, 1) and s == (1, 1, 1) and p == (0, 0, 0) and _same_grid(d) and d.Cin * d.Cout <= 128 * 128 and d.tile_hint != 7:
-        return "1x1"
-    if lib.ssbev_conv_chunk_groups(C.byref(d), 2) > 0:
-        return "dh"
-    if d.tile_hint != 7:
-        forced = capi.ConvDims(*[getattr(d, n) for n in FIELDS])
-        forced.tile_hint = 7
-        if lib.ssbev_conv_bwd_weight_workspace(C.byref(forced)) != lib.ssbev_conv_bwd_weight_workspace(C.byref(d)):
-            return "lds"
-    if (not d.transposed and s == (1, 1, 1) and _same_grid(d) and d.Wo % 4 == 0 and (d.B * d.Do * d.Ho * d.Wo) % 8 == 0
-            and all(2 * pp == dd * (kk - 1) for pp, dd, kk in zip(p, dl, k))):
-        return "cf"
-    return "generic"
+    """The kind select_wgrad takes, as ssbev_conv_wgrad_plan_query numbers it, under the labels of the snapshot."""
+    plan = capi.ConvWgradPlan()
+    q = lib.ssbev_conv_wgrad_plan_query
+    q.restype, q.argtypes = capi.SIGNATURES["ssbev_conv_wgrad_plan_query"]
+    rc = q(C.byref(d), C.byref(plan))
+    assert rc == 0, rc
+    return WGRAD_KINDS[plan.kind]
 
 
 def record(lib, row):
