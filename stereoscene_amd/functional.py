@@ -11,6 +11,7 @@ which is the layout the kernels read and write; nothing is permuted on the way i
 """
 import ctypes as C
 import math
+from typing import NamedTuple
 
 import os
 
@@ -586,6 +587,30 @@ def _thin_out_run(lib, src, weight5, bias, out, d, mode):
                                        capi.ptr(ws), ws.numel(), capi.stream()), "ssbev_conv_thin_run")
 
 
+def _conv_grads(device, weight, want, bias_leaf, reads, weight_gradient, data_gradient, bias_gradient=None):
+    """The order in which a conv backward issues its gradients -> (gx, gw, gb); ``want``: which of the three autograd asks for.
+    The weight gradient is a leaf of the backward chain: on the side stream (streams.py) it runs NEXT to the data gradient and
+    the normalisation passes that follow it instead of in front of them, and so does the gradient of a leaf bias (a column sum
+    of gy); ``reads`` are the tensors the side stream has to wait for.  Then the data gradient, then whatever did not go aside."""
+    want_gx, want_gw, want_gb = want
+    gx = gw = gb = None
+    gw_side = want_gw and streams.wgrad_on_side(weight)
+    gb_side = gw_side and want_gb and bias_leaf
+    if gw_side:
+        with streams.on_side(device, *reads) as side:
+            gw = weight_gradient()
+            if gb_side:
+                gb = bias_gradient()
+            side.publish(gw, gb)
+    if want_gx:
+        gx = data_gradient()
+    if want_gw and not gw_side:
+        gw = weight_gradient()
+    if want_gb and not gb_side:
+        gb = bias_gradient()
+    return gx, gw, gb
+
+
 class _ConvNd(torch.autograd.Function):
     """x logical [B,Cin,D,H,W] (channels-last memory), weight in the torch layout (5-D)."""
 
@@ -655,7 +680,6 @@ class _ConvNd(torch.autograd.Function):
         elif cpad:
             w5 = None                                       # nobody needs the padded operands
         d = _conv_dims(tuple(xcl.shape), tuple(w5.shape), *args) if w5 is not None else d0
-        gx = gw = gb = None
 
         def weight_gradient():
             pointwise = (not transposed and tuple(weight.shape[2:]) == (1, 1, 1) and stride == (1, 1, 1) and padding == (0, 0, 0)
@@ -683,18 +707,7 @@ class _ConvNd(torch.autograd.Function):
                 gw = gwp if tuple(wshape) == tuple(weight.shape) else gwp[: weight.shape[0], : weight.shape[1]].contiguous()
             return gw
 
-        # the weight gradient is a leaf of the backward chain: on the side stream it runs NEXT to the data gradient and the
-        # normalisation passes that follow it instead of in front of them (streams.py)
-        gw_side = want_gw and streams.wgrad_on_side(weight)
-        want_gb = has_bias and ctx.needs_input_grad[2]
-        gb_side = gw_side and want_gb and ctx.bias_leaf
-        if gw_side:
-            with streams.on_side(gy.device, xcl, gcl0, gcl) as side:
-                gw = weight_gradient()
-                if gb_side:                                   # the bias gradient (a column sum of gy) is a leaf as well
-                    gb = gcl0.reshape(-1, Cout_g).sum(0)
-                side.publish(gw, gb)
-        if want_gx:
+        def data_gradient():
             dd, gdl, wd = (d0, gcl0, weight.detach()) if thin_d else (d, gcl, w5)
             slot = ctx.slot if (not kpad and not thin_d and lib.ssbev_conv_kernel_class(C.byref(dd), 1) not in (4, 5)) else None
             into = _slot_target(slot, xcl)
@@ -714,12 +727,18 @@ class _ConvNd(torch.autograd.Function):
                 slot.buf = gxcl
             if kpad:
                 gxcl = gxcl[..., : xcl.shape[-1] - kpad]
-            gx = from_cl(gxcl)
-        if want_gw and not gw_side:
-            gw = weight_gradient()
-        if want_gb and not gb_side:
-            gb = gcl0.reshape(-1, Cout_g).sum(0)
-        return gx, gw, gb, None, None, None, None, None, None, None
+            return from_cl(gxcl)
+
+        want = (want_gx, want_gw, has_bias and ctx.needs_input_grad[2])
+        return _conv_grads(gy.device, weight, want, ctx.bias_leaf, (xcl, gcl0, gcl), weight_gradient, data_gradient,
+                           lambda: gcl0.reshape(-1, Cout_g).sum(0)) + (None,) * 7
+
+
+def _conv16_family(lib, d, mode):
+    """Span family of a bf16-storage conv launch (the class query only when a timer listens)."""
+    if KERNEL_TIMER is None:
+        return "conv_gather16"
+    return {17: "conv_tap16", 19: "conv_wide16"}.get(lib.ssbev_conv_kernel_class(C.byref(d), mode), "conv_gather16")
 
 
 class _ConvNd16(torch.autograd.Function):
@@ -738,8 +757,7 @@ class _ConvNd16(torch.autograd.Function):
         d.precision = 3 if out_fp32 else 2
         y = torch.empty(d.B, d.Do, d.Ho, d.Wo, d.Cout, dtype=torch.float32 if out_fp32 else torch.bfloat16, device=x.device)
         b = bias.detach().float().contiguous() if bias is not None else None
-        fam = {17: "conv_tap16", 19: "conv_wide16"}.get(lib.ssbev_conv_kernel_class(C.byref(d), 0), "conv_gather16") if KERNEL_TIMER is not None else "conv_gather16"
-        with _span(fam, conv_flops(d), conv_bytes(d) / 2.0, _conv_tag(d, "fwd")):
+        with _span(_conv16_family(lib, d, 0), conv_flops(d), conv_bytes(d) / 2.0, _conv_tag(d, "fwd")):
             wp = _packed(weight.detach(), d, 0)
             capi.check(lib.ssbev_conv_fwd_bf16(capi.ptr(xcl), capi.ptr(wp), capi.ptr(b), capi.ptr(y), C.byref(d), capi.stream()),
                        "ssbev_conv_fwd_bf16")
@@ -762,8 +780,6 @@ class _ConvNd16(torch.autograd.Function):
         Cout_g = gcl.shape[-1]
         d = _conv_dims(tuple(xcl.shape), tuple(weight.shape), stride, padding, dilation, transposed, output_padding)
         d.precision = 2
-        want_gx, want_gw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gx = gw = gb = None
 
         def weight_gradient():
             if (WIDE16_WGRAD == "wino" and not transposed and lib.ssbev_conv_kernel_class(C.byref(d), 0) == 19
@@ -778,46 +794,23 @@ class _ConvNd16(torch.autograd.Function):
                                                           ws.numel(), capi.stream()), "ssbev_conv_bwd_weight_bf16")
             return gwp
 
-        gw_side = want_gw and streams.wgrad_on_side(weight)
-        want_gb = has_bias and ctx.needs_input_grad[2]
-        gb_side = gw_side and want_gb and ctx.bias_leaf
-        if gw_side:
-            with streams.on_side(gy.device, xcl, gcl) as side:
-                gw = weight_gradient()
-                if gb_side:
-                    gb = gcl.reshape(-1, Cout_g).sum(0, dtype=torch.float32)
-                side.publish(gw, gb)
-        if want_gx:
+        def data_gradient():
             into = _slot_target(ctx.slot, xcl)
             if into is not None:
                 d.accumulate = 1
             gxcl = into if into is not None else torch.empty_like(xcl)
-            fam = {17: "conv_tap16", 19: "conv_wide16"}.get(lib.ssbev_conv_kernel_class(C.byref(d), 1), "conv_gather16") if KERNEL_TIMER is not None else "conv_gather16"
-            with _span(fam, conv_flops(d), conv_bytes(d) / 2.0, _conv_tag(d, "dgrad")):
+            with _span(_conv16_family(lib, d, 1), conv_flops(d), conv_bytes(d) / 2.0, _conv_tag(d, "dgrad")):
                 wpt = _packed(weight.detach(), d, 1)
                 capi.check(lib.ssbev_conv_bwd_data_bf16(capi.ptr(gcl), capi.ptr(wpt), capi.ptr(gxcl), C.byref(d), capi.stream()),
                            "ssbev_conv_bwd_data_bf16")
             d.accumulate = 0
             if ctx.slot is not None:
                 ctx.slot.buf = gxcl
-            gx = from_cl(gxcl)
-        if want_gw and not gw_side:
-            gw = weight_gradient()
-        if want_gb and not gb_side:
-            gb = gcl.reshape(-1, Cout_g).sum(0, dtype=torch.float32)
-        return gx, gw, gb, None, None, None, None, None, None, None, None
+            return from_cl(gxcl)
 
-
-def _conv16_route(x, weight5, bias, st, pd, dl, transposed, op, relu=False):
-    """bf16 storage mode: the convolution on csrc/conv_bf16.hip when its channel counts allow 16-byte bf16 voxel-line pieces
-    (Cin % 8 == 0 and Cout % 8 == 0), else None (the caller keeps its fp32 island: the 1- / 2- / 20-channel layers)."""
-    if not (storage_bf16() and x.is_cuda and TILE_HINT in (0, 7, 9)):
-        return None
-    cin = weight5.shape[0] if transposed else weight5.shape[1]
-    cout = weight5.shape[1] if transposed else weight5.shape[0]
-    if cin % 8 != 0 or cout % 8 != 0:        # (the Cout-channel gradient is a bf16 SOURCE in backward)
-        return None
-    return _ConvNd16.apply(x, weight5, bias, st, pd, dl, transposed, op, _slot_of(x), bool(relu), False)
+        want = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2])
+        return _conv_grads(gy.device, weight, want, ctx.bias_leaf, (xcl, gcl), weight_gradient, data_gradient,
+                           lambda: gcl.reshape(-1, Cout_g).sum(0, dtype=torch.float32)) + (None,) * 8
 
 
 # bf16 storage mode: the wide stride-1 3x3x3 layers on grids with W % 16 == 0 (voxel encoder level 0, head conv, the 64 -> 64
@@ -826,16 +819,6 @@ WIDE16 = os.environ.get("SSBEV_WIDE16", "1") != "0"
 # ... and their weight gradient on the LDS-ring kernel wgrad_ring16_kernel ("direct", default) or on the Winograd-domain product
 # (input transform + adjoint + batched bf16 library GEMM: "wino", kept for A/B runs)
 WIDE16_WGRAD = os.environ.get("SSBEV_WIDE16_WGRAD", "direct")
-
-
-def _wide16_applicable(x, weight, st, pd, dl):
-    if x.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or st != (1, 1, 1) or pd != (1, 1, 1) or dl != (1, 1, 1):
-        return False
-    if weight.shape[0] % 8 or weight.shape[1] % 8:
-        return False
-    d = _conv_dims((x.shape[0], x.shape[2], x.shape[3], x.shape[4], x.shape[1]), tuple(weight.shape), st, pd, dl, False, (0, 0, 0))
-    d.precision = 2
-    return capi.load().ssbev_conv_kernel_class(C.byref(d), 0) == 19
 
 
 def _wino_wgrad_bf16(xcl, gcl, weight):
@@ -865,41 +848,6 @@ WINOGRAD = os.environ.get("SSBEV_WINOGRAD", "1") != "0"   # wide 3x3x3 stride-1 
 # bf16 storage mode: wide stride-1 3x3(x3) layers on the F(2,3) Winograd pipeline with bf16 tensors on both sides (1), or on the
 # direct bf16 MFMA kernels (0): 3.4x / 2.25x fewer multiply-adds against 8x / 4x larger transformed tensors
 WINO_BF16S = os.environ.get("SSBEV_WINO_BF16S", "1") != "0"
-
-
-def conv3d(x, weight, bias=None, stride=1, padding=0, dilation=1, relu=False):
-    """F.conv3d replacement (groups=1): the MFMA implicit-GEMM kernels, or Winograd F(2x2x2,3x3x3) for the wide
-    stride-1 3x3x3 layers."""
-    st, pd, dl = _triple(stride, 3), _triple(padding, 3), _triple(dilation, 3)
-    if storage_bf16() and x.is_cuda and TILE_HINT in (0, 7, 9):
-        if WIDE16 and _wide16_applicable(x, weight, st, pd, dl):
-            return _ConvNd16.apply(x, weight, bias, st, pd, dl, False, (0, 0, 0), _slot_of(x), bool(relu), False)
-        if WINOGRAD and WINO_BF16S and wino_conv3d_applicable(x, weight, st, pd, dl):
-            y = _WinoConv.apply(x, weight, _slot_of(x))
-            y = y if bias is None else y + _like_act(bias, y).view(1, -1, 1, 1, 1)
-            return torch.relu(y) if relu else y
-        y = _conv16_route(x, weight, bias, st, pd, dl, False, (0, 0, 0), relu)
-        if y is not None:
-            return y
-        return _to_act(_ConvNd.apply(x, weight, bias, st, pd, dl, False, (0, 0, 0), None, bool(relu)))
-    if relu:    # epilogue ReLU of the direct kernels (the MIE block's two conv -> ReLU pairs, VT:250-258); elsewhere a norm follows
-        gemm = (GEMM_LAYERS and TILE_HINT == 0 and PRECISION == "fp32" and tuple(weight.shape[2:]) == (1, 1, 1)
-                and st == (1, 1, 1) and pd == (0, 0, 0) and weight.shape[1] >= GEMM_MIN_CIN)
-        if not x.is_cuda or gemm or (WINOGRAD and TILE_HINT == 0 and wino_conv3d_applicable(x, weight, st, pd, dl)):
-            return torch.relu(conv3d(x, weight, bias, stride, padding, dilation))
-        return _ConvNd.apply(x, weight, bias, st, pd, dl, False, (0, 0, 0), _slot_of(x), True)
-    if (GEMM_LAYERS and TILE_HINT == 0 and PRECISION == "fp32" and x.is_cuda and tuple(weight.shape[2:]) == (1, 1, 1)
-            and st == (1, 1, 1) and pd == (0, 0, 0) and weight.shape[1] >= GEMM_MIN_CIN):
-        return linear_cl(x, weight, bias)
-    if WINOGRAD and TILE_HINT == 0 and wino_conv3d_applicable(x, weight, st, pd, dl):
-        B, Cin, D, H, W = x.shape
-        if tuple(weight.shape[2:]) == (3, 3, 3) and H % 4 == 0 and W % 4 == 0 and \
-                _wino_df_applicable(B, D, H, W, Cin, weight.shape[0]):
-            y = _WinoConvDF.apply(x, weight, _slot_of(x))
-        else:
-            y = _WinoConv.apply(x, weight, _slot_of(x))
-        return y if bias is None else y + bias.view(1, -1, 1, 1, 1)
-    return _ConvNd.apply(x, weight, bias, st, pd, dl, False, (0, 0, 0), _slot_of(x))
 
 
 # -------------------------------------------------------------------------------------------------
@@ -1127,45 +1075,6 @@ GEMM_LAYERS = os.environ.get("SSBEV_GEMM_LAYERS", "1") != "0"
 GEMM_MIN_CIN = int(os.environ.get("SSBEV_GEMM_MIN_CIN", "512"))       # pointwise convs narrower than this stay on the HIP kernels
 
 
-def _deconv_k_eq_s_gemm(x, weight, bias, k):
-    if tuple(k) == (1, 1, 1) and own_gemm_site("deconv") and own_gemm_site("linear") and weight.shape[1] % 4 == 0:
-        # k = s = 1 (SECONDFPN3D's first branch, FPN:53-69) is a pointwise layer: the plain NT / NN / skinny-TN products of linear_cl.
-        # Through the depth-to-space table of the general k == s path its weight gradient ran at 26 TF/s (0.33 ms for 8.6 GF:
-        # profiles/r6c layer table) where the skinny TN kernel needs 0.12 ms for the same product.
-        return linear_cl(x, weight.reshape(weight.shape[0], weight.shape[1]).t(), bias)
-    xcl = to_cl(_f32(x, "deconv_gemm"))
-    B, D, H, W, Ci = xcl.shape
-    Co = weight.shape[1]
-    kd, kh, kw = k
-    if own_gemm_site("deconv") and Co % 64 == 0 and Ci % 4 == 0:
-        return from_cl(_DeconvKS.apply(xcl, weight, bias, (int(kd), int(kh), int(kw))))
-    w2 = weight.permute(0, 2, 3, 4, 1).reshape(Ci, kd * kh * kw * Co)
-    fl = 2.0 * B * D * H * W * Ci * kd * kh * kw * Co
-    nby = 4.0 * (xcl.numel() + w2.numel() + B * D * H * W * kd * kh * kw * Co)
-    mult = 3.0 if (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad)) else 1.0
-    with _span("gemm_lib", fl * mult, nby * mult, f"fwd   deconv k=s {Ci}->{Co} k{kd}{kh}{kw}"):
-        g = torch.mm(xcl.reshape(-1, Ci), w2).view(B, D, H, W, kd, kh, kw, Co)
-    y = g.permute(0, 1, 4, 2, 5, 3, 6, 7).reshape(B, D * kd, H * kh, W * kw, Co)
-    if bias is not None:
-        y = y + bias
-    return from_cl(y)
-
-
-def conv_transpose3d(x, weight, bias=None, stride=1, padding=0, output_padding=0):
-    """F.conv_transpose3d replacement (weight [Cin, Cout, kd, kh, kw])."""
-    st, pd, op = _triple(stride, 3), _triple(padding, 3), _triple(output_padding, 3)
-    if storage_bf16() and x.is_cuda and TILE_HINT in (0, 9):
-        y = _conv16_route(x, weight, bias, st, pd, (1, 1, 1), True, op)
-        if y is not None:
-            return y
-        return _to_act(_ConvNd.apply(x, weight, bias, st, pd, (1, 1, 1), True, op))
-    if (GEMM_LAYERS and TILE_HINT == 0 and PRECISION == "fp32" and x.is_cuda and tuple(weight.shape[2:]) == tuple(st)
-            and pd == (0, 0, 0) and op == (0, 0, 0) and weight.shape[0] >= 128):
-        return _deconv_k_eq_s_gemm(x, weight, bias, tuple(st))
-    return _ConvNd.apply(x, weight, bias, _triple(stride, 3), _triple(padding, 3), (1, 1, 1), True,
-                         _triple(output_padding, 3))
-
-
 # A 3x3 convolution with dilation d and padding d only couples pixels of the same residue class modulo d: it is d*d
 # independent ordinary 3x3 / pad 1 convolutions on the (H/d) x (W/d) sub-grids.  The ASPP branches of DepthNet (640 -> 640,
 # dilation 6 / 12 / 18 on the 48 x 160 map) are therefore sent through the Winograd path as a batch of d*d small images
@@ -1193,18 +1102,28 @@ def wino2d_axis_tiles(n, d):
     return sum(-(-(-(-(n - ph) // d)) // 2) for ph in range(min(d, n)))
 
 
-def _wino_dilated_applicable(x, weight, d):
-    H, W = int(x.shape[-2]), int(x.shape[-1])
+def _wino_dilated_fits(H, W, cin, d):
     th, tw = wino2d_axis_tiles(H, d), wino2d_axis_tiles(W, d)
-    return (max(th, tw) <= WINO_DILATED_AXIS_CAP and weight.shape[1] % 4 == 0
+    return (max(th, tw) <= WINO_DILATED_AXIS_CAP and cin % 4 == 0
             and th * tw <= WINO_DILATED_MAX_TILES * (-(-H // 2)) * (-(-W // 2)))
+
+
+def _wino_dilated_applicable(x, weight, d):
+    return _wino_dilated_fits(int(x.shape[-2]), int(x.shape[-1]), weight.shape[1], d)
+
+
+def _polyphase_grid(H, W, d):
+    """The map padded to multiples of 2d, or None when that costs more than POLYPHASE_MAX_PAD times the pixels."""
+    Hp, Wp = -(-H // (2 * d)) * 2 * d, -(-W // (2 * d)) * 2 * d
+    return (Hp, Wp) if Hp * Wp <= POLYPHASE_MAX_PAD * H * W else None
 
 
 def _dilated_polyphase(x, weight, d):
     B, Cc, H, W = x.shape
-    Hp, Wp = -(-H // (2 * d)) * 2 * d, -(-W // (2 * d)) * 2 * d
-    if Hp * Wp > POLYPHASE_MAX_PAD * H * W:
+    grid = _polyphase_grid(H, W, d)
+    if grid is None:
         return None
+    Hp, Wp = grid
     xp = torch.nn.functional.pad(x, [0, Wp - W, 0, Hp - H]) if (Hp != H or Wp != W) else x
     xs = xp.reshape(B, Cc, Hp // d, d, Wp // d, d).permute(0, 3, 5, 1, 2, 4).reshape(B * d * d, Cc, Hp // d, Wp // d)
     ys = conv2d(xs, weight, None, 1, 1, 1)
@@ -1213,43 +1132,168 @@ def _dilated_polyphase(x, weight, d):
     return y[:, :, :H, :W]
 
 
+# -------------------------------------------------------------------------------------------------
+# conv routing: which leaf serves a conv3d / conv2d / conv_transpose3d call
+# -------------------------------------------------------------------------------------------------
+# ONE place decides and ONE place executes, like select_conv_path in csrc/conv_mfma.hip one level down.  `_conv_route` is a pure
+# function of shapes and module switches (read at call time: tests and A/B runs assign to them) that states the order of the
+# routes top to bottom and returns a `_Route`; `_conv_run` is the only caller of the leaves (_ConvNd, _ConvNd16, _WinoConv,
+# _WinoConvDF, linear_cl, _DeconvKS, torch.mm, torch.relu) and of the steps around them.  The entry points normalise their
+# arguments (conv2d lifts its shapes to a depth-1 volume) and call the two.  A new route is one kind, one line in `_conv_route` and
+# one case in `_conv_run`; tests/test_conv_routes_snapshot.py pins what every layer shape of the workload gets under every switch.
+#
+# Order.  bf16 storage (GPU tensor, admitted tile hint): wide16 ring (conv3d) | polyphase batch (conv2d) | bf16 Winograd | bf16
+# direct (both channel counts % 8 == 0) | fp32 island, cast back.  Otherwise, conv_transpose3d: k == s GEMM (k = s = 1 as a
+# linear layer | own kernels | library mm) | direct.  conv3d / conv2d: ReLU fused into the direct kernel unless one of the next
+# three or a non-GPU tensor takes the call (then ReLU outside) | pointwise GEMM | dilated 3x3 (conv2d): strided-tile Winograd |
+# polyphase batch | Winograd, depth-fused where it applies | direct.
+#
+# What a route fixes besides the leaf -- each was a detail of a call site once, and is kept as found:
+#   * the bias goes INTO the direct / GEMM kernels and is added AFTER the Winograd pipelines and the polyphase batch;
+#   * the ReLU is fused into the direct kernels and applied after everything else;
+#   * the `fork` gradient slot is taken off the input alias (_slot_of) exactly when the leaf receives it.  A route that took it
+#     and returned a fresh gradient would double-count silently.  Quirks: the fp32 islands, conv2d's bf16 direct route (the parent
+#     asked the lifted view, which carries no slot) and the whole fp32 side of conv_transpose3d never take it;
+#   * which TILE_HINT values admit the bf16 routes differs per entry point (_BF16_HINTS): also a quirk; any hint but 0 takes the
+#     fp32 GEMM and Winograd routes away (the hint is a tuning hook of the direct kernels).
+_BF16_HINTS = {"conv3d": (0, 7, 9), "conv2d": (0, 9), "conv_transpose3d": (0, 9)}
+
+
+class _Route(NamedTuple):
+    kind: str                         # the case of _conv_run
+    geom: tuple                       # (stride, padding, dilation, transposed, output_padding) of the leaf (conv2d: depth-1 volume)
+    take_slot: bool = True            # the leaf gets the input's gradient slot (False: it stays on the alias)
+    bias_after: bool = False          # added to the leaf's result (False: passed into the leaf)
+    relu_fused: bool = False          # in the leaf's epilogue ...
+    relu_after: bool = False          # ... or torch.relu on the result
+    cast: bool = False                # fp32 island: _to_act on the result
+    lift: bool = False                # conv2d on a 5-D leaf: unsqueeze(2) going in, squeeze(2) coming out
+    dil: int = 1                      # dilation of the strided-tile Winograd route / of the polyphase batch
+    out_fp32: bool = False            # _ConvNd16: fp32 result (no route asks for it yet)
+
+
+def _pointwise_gemm(wshape, st, pd):
+    """A wide 1x1(x1) / stride 1 layer: the plain GEMM of linear_cl (fp32 without a tile hint)."""
+    return (GEMM_LAYERS and TILE_HINT == 0 and PRECISION == "fp32" and tuple(wshape[2:]) == (1, 1, 1) and st == (1, 1, 1)
+            and pd == (0, 0, 0) and wshape[1] >= GEMM_MIN_CIN)
+
+
+def _dilated_same_3x3(wshape, st, pd, dl):
+    """A wide 2-D 3x3 / stride 1 layer with dilation = padding = d > 1 (lifted to a depth-1 volume): the ASPP branches."""
+    return (tuple(wshape[2:]) == (1, 3, 3) and st == (1, 1, 1) and dl[1] == dl[2] and dl[1] > 1 and pd[1:] == dl[1:]
+            and min(wshape[0], wshape[1]) >= 64)
+
+
+def _conv_route(entry, xshape, wshape, stride, padding, dilation, transposed, output_padding, relu, is_cuda):
+    st, pd, dl, k = tuple(stride), tuple(padding), tuple(dilation), tuple(wshape[2:])
+    B, _, D, H, W = xshape
+    cin, cout = (wshape[0], wshape[1]) if transposed else (wshape[1], wshape[0])
+    lift = entry == "conv2d"
+
+    def route(kind, **facts):
+        return _Route(kind, (st, pd, dl, transposed, tuple(output_padding)), **facts)
+    wino = not transposed and WINOGRAD and _wino_applicable(is_cuda, xshape, wshape, st, pd, dl)
+    dilated = lift and WINOGRAD and is_cuda and _dilated_same_3x3(wshape, st, pd, dl)
+    if storage_bf16() and is_cuda and TILE_HINT in _BF16_HINTS[entry]:
+        if entry == "conv3d" and WIDE16 and k == (3, 3, 3) and st == pd == dl == (1, 1, 1) and cin % 8 == 0 and cout % 8 == 0:
+            d = _conv_dims((B, D, H, W, cin), tuple(wshape), st, pd, dl, False, (0, 0, 0))
+            d.precision = 2
+            if capi.load().ssbev_conv_kernel_class(C.byref(d), 0) == 19:          # conv_wide16_kernel takes it
+                return route("conv16", relu_fused=relu)
+        if dilated and DILATED_POLYPHASE and WINO_BF16S and _polyphase_grid(H, W, dl[1]):
+            return route("polyphase", take_slot=False, bias_after=True, dil=dl[1])
+        if wino and WINO_BF16S:
+            return route("wino", bias_after=True, relu_after=relu, lift=lift)
+        if cin % 8 == 0 and cout % 8 == 0:       # 16-byte bf16 voxel-line pieces (the Cout-channel gradient is a bf16 SOURCE in backward)
+            return route("conv16", relu_fused=relu, lift=lift, take_slot=not lift)       # (quirk: conv2d leaves the slot on the alias)
+        return route("convnd", take_slot=False, relu_fused=relu, cast=True, lift=lift)       # the 1- / 2- / 20-channel layers
+    if transposed:
+        if GEMM_LAYERS and TILE_HINT == 0 and PRECISION == "fp32" and is_cuda and k == st and pd == (0, 0, 0) and \
+                tuple(output_padding) == (0, 0, 0) and cin >= 128:
+            # k = s = 1 (SECONDFPN3D's first branch, FPN:53-69) is a pointwise layer: the plain NT / NN / skinny-TN products of
+            # linear_cl.  Through the depth-to-space table of the general k == s path its weight gradient ran at 26 TF/s (0.33 ms
+            # for 8.6 GF: profiles/r6c layer table) where the skinny TN kernel needs 0.12 ms for the same product.
+            if k == (1, 1, 1) and own_gemm_site("deconv") and own_gemm_site("linear") and cout % 4 == 0:
+                return route("linear", take_slot=False)
+            return route("deconv_ks" if own_gemm_site("deconv") and cout % 64 == 0 and cin % 4 == 0 else "deconv_mm", take_slot=False)
+        return route("convnd", take_slot=False)                 # (quirk: no fp32 route of conv_transpose3d takes the slot)
+    gemm = is_cuda and _pointwise_gemm(wshape, st, pd)
+    wino = wino and TILE_HINT == 0
+    if gemm:                                     # wide pointwise conv = plain GEMM on the channels-last buffer
+        return route("linear", take_slot=False, relu_after=relu)
+    if dilated and TILE_HINT == 0:
+        if WINO_DILATED and PRECISION == "fp32" and _wino_dilated_fits(H, W, cin, dl[1]):
+            return route("wino", bias_after=True, lift=True, dil=dl[1])
+        if DILATED_POLYPHASE and _polyphase_grid(H, W, dl[1]):
+            return route("polyphase", take_slot=False, bias_after=True, dil=dl[1])
+    if wino:
+        df = k == (3, 3, 3) and H % 4 == 0 and W % 4 == 0 and _wino_df_applicable(B, D, H, W, cin, cout)
+        return route("wino_df" if df else "wino", bias_after=True, relu_after=relu, lift=lift)
+    # epilogue ReLU of the direct kernels (the MIE block's two conv -> ReLU pairs, VT:250-258); elsewhere a norm follows
+    return route("convnd", relu_fused=relu and is_cuda, relu_after=relu and not is_cuda, lift=lift)
+
+
+def _conv_run(r, x, weight, bias):
+    slot = _slot_of(x) if r.take_slot else None
+    stride, _, _, transposed, _ = r.geom
+    x5, w5 = (x.unsqueeze(2), weight.unsqueeze(2)) if r.lift else (x, weight)
+    if r.kind == "conv16":
+        y = _ConvNd16.apply(x5, w5, bias, *r.geom, slot, r.relu_fused, r.out_fp32)
+    elif r.kind == "convnd":
+        y = _ConvNd.apply(x5, w5, bias, *r.geom, slot, r.relu_fused)
+    elif r.kind == "wino":
+        y = _WinoConv.apply(x5, w5, slot, r.dil)
+    elif r.kind == "wino_df":
+        y = _WinoConvDF.apply(x5, w5, slot)
+    elif r.kind == "linear":                     # (a k = s = 1 deconv: weight [Cin, Cout, 1, 1, 1])
+        y = linear_cl(x, weight.reshape(weight.shape[0], weight.shape[1]).t() if transposed else weight, bias)
+    elif r.kind == "polyphase":                  # d * d sub-images through conv2d again (their route: undilated Winograd)
+        y = _dilated_polyphase(x, weight, r.dil)
+    elif r.kind == "deconv_ks":
+        y = from_cl(_DeconvKS.apply(to_cl(_f32(x, "deconv_gemm")), weight, bias, stride))
+    elif r.kind == "deconv_mm":                  # the library's k == s deconv: GEMM, depth-to-space copy, bias
+        xcl = to_cl(_f32(x, "deconv_gemm"))
+        (B, D, H, W, Ci), Co, (kd, kh, kw) = xcl.shape, weight.shape[1], stride
+        w2 = weight.permute(0, 2, 3, 4, 1).reshape(Ci, kd * kh * kw * Co)
+        fl = 2.0 * B * D * H * W * Ci * kd * kh * kw * Co
+        nby = 4.0 * (xcl.numel() + w2.numel() + B * D * H * W * kd * kh * kw * Co)
+        mult = 3.0 if (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad)) else 1.0
+        with _span("gemm_lib", fl * mult, nby * mult, f"fwd   deconv k=s {Ci}->{Co} k{kd}{kh}{kw}"):
+            g = torch.mm(xcl.reshape(-1, Ci), w2).view(B, D, H, W, kd, kh, kw, Co)
+        y = g.permute(0, 1, 4, 2, 5, 3, 6, 7).reshape(B, D * kd, H * kh, W * kw, Co)
+        y = from_cl(y if bias is None else y + bias)
+    else:
+        raise capi.SsbevError(f"conv route {r.kind!r} has no executor")
+    if r.cast:
+        y = _to_act(y)
+    if r.lift:
+        y = y.squeeze(2)
+    if r.bias_after and bias is not None:
+        y = y + _like_act(bias, y).view((1, -1) + (1,) * (y.dim() - 2))
+    return torch.relu(y) if r.relu_after else y
+
+
+def conv3d(x, weight, bias=None, stride=1, padding=0, dilation=1, relu=False):
+    """F.conv3d replacement (groups=1): the MFMA implicit-GEMM kernels, or Winograd F(2x2x2,3x3x3) for the wide
+    stride-1 3x3x3 layers."""
+    r = _conv_route("conv3d", x.shape, weight.shape, _triple(stride, 3), _triple(padding, 3), _triple(dilation, 3), False, (0, 0, 0),
+                    bool(relu), x.is_cuda)
+    return _conv_run(r, x, weight, bias)
+
+
 def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1):
     """F.conv2d replacement: a depth-1 volume through the same kernels (groups=1); wide 3x3 stride-1 layers via
     Winograd F(2x2,3x3)."""
-    s, p, dl = _triple(stride, 2), _triple(padding, 2), _triple(dilation, 2)
-    if storage_bf16() and x.is_cuda and TILE_HINT in (0, 9):
-        x5, w5 = x.unsqueeze(2), weight.unsqueeze(2)
-        if (DILATED_POLYPHASE and WINOGRAD and WINO_BF16S and tuple(weight.shape[2:]) == (3, 3) and s == (1, 1) and dl[0] == dl[1]
-                and dl[0] > 1 and p == dl and min(weight.shape[0], weight.shape[1]) >= 64):
-            y = _dilated_polyphase(x, weight, dl[0])
-            if y is not None:
-                return y if bias is None else y + _like_act(bias, y).view(1, -1, 1, 1)
-        if WINOGRAD and WINO_BF16S and wino_conv3d_applicable(x5, w5, (1,) + s, (0,) + p, (1,) + dl):
-            y = _WinoConv.apply(x5, w5, _slot_of(x)).squeeze(2)
-            return y if bias is None else y + _like_act(bias, y).view(1, -1, 1, 1)
-        y = _conv16_route(x5, w5, bias, (1,) + s, (0,) + p, (1,) + dl, False, (0, 0, 0))
-        if y is None:
-            y = _to_act(_ConvNd.apply(x5, w5, bias, (1,) + s, (0,) + p, (1,) + dl, False, (0, 0, 0)))
-        return y.squeeze(2)
-    if (GEMM_LAYERS and TILE_HINT == 0 and PRECISION == "fp32" and x.is_cuda and tuple(weight.shape[2:]) == (1, 1)
-            and s == (1, 1) and p == (0, 0) and weight.shape[1] >= GEMM_MIN_CIN):
-        return linear_cl(x, weight, bias)           # wide pointwise conv = plain GEMM on the channels-last buffer
-    if (WINO_DILATED and WINOGRAD and TILE_HINT == 0 and PRECISION == "fp32" and x.is_cuda and tuple(weight.shape[2:]) == (3, 3)
-            and s == (1, 1) and dl[0] == dl[1] and dl[0] > 1 and p == dl and min(weight.shape[0], weight.shape[1]) >= 64
-            and _wino_dilated_applicable(x, weight, dl[0])):
-        y = _WinoConv.apply(x.unsqueeze(2), weight.unsqueeze(2), _slot_of(x), dl[0]).squeeze(2)
-        return y if bias is None else y + bias.view(1, -1, 1, 1)
-    if (DILATED_POLYPHASE and WINOGRAD and TILE_HINT == 0 and x.is_cuda and tuple(weight.shape[2:]) == (3, 3) and s == (1, 1)
-            and dl[0] == dl[1] and dl[0] > 1 and p == dl and min(weight.shape[0], weight.shape[1]) >= 64):
-        y = _dilated_polyphase(x, weight, dl[0])
-        if y is not None:
-            return y if bias is None else y + bias.view(1, -1, 1, 1)
-    x5, w5 = x.unsqueeze(2), weight.unsqueeze(2)
-    if WINOGRAD and TILE_HINT == 0 and wino_conv3d_applicable(x5, w5, (1,) + s, (0,) + p, (1,) + dl):
-        y = _WinoConv.apply(x5, w5, _slot_of(x)).squeeze(2)
-        return y if bias is None else y + bias.view(1, -1, 1, 1)
-    y = _ConvNd.apply(x5, w5, bias, (1,) + s, (0,) + p, (1,) + dl, False, (0, 0, 0), _slot_of(x))
-    return y.squeeze(2)
+    r = _conv_route("conv2d", (*x.shape[:2], 1, *x.shape[2:]), (*weight.shape[:2], 1, *weight.shape[2:]), (1,) + _triple(stride, 2),
+                    (0,) + _triple(padding, 2), (1,) + _triple(dilation, 2), False, (0, 0, 0), False, x.is_cuda)
+    return _conv_run(r, x, weight, bias)
+
+
+def conv_transpose3d(x, weight, bias=None, stride=1, padding=0, output_padding=0):
+    """F.conv_transpose3d replacement (weight [Cin, Cout, kd, kh, kw])."""
+    r = _conv_route("conv_transpose3d", x.shape, weight.shape, _triple(stride, 3), _triple(padding, 3), (1, 1, 1), True,
+                    _triple(output_padding, 3), False, x.is_cuda)
+    return _conv_run(r, x, weight, bias)
 
 
 # -------------------------------------------------------------------------------------------------
@@ -1521,7 +1565,6 @@ class _WinoConvDF(torch.autograd.Function):
         gcl = to_cl(gy)
         lib = capi.load()
         w = weight.detach().contiguous()
-        gx = gw = None
 
         def weight_gradient():
             R = B * D * (H // 4) * (W // 4)
@@ -1536,20 +1579,15 @@ class _WinoConvDF(torch.autograd.Function):
                                                      ws.numel(), capi.stream()), "ssbev_wino43_df_wgrad")
             return gwt
 
-        gw_side = ctx.needs_input_grad[1] and streams.wgrad_on_side(weight)
-        if gw_side:                          # leaf of the backward chain: next to the data gradient, not in front of it
-            with streams.on_side(gy.device, gcl, P) as side:
-                gw = weight_gradient()
-                side.publish(gw)
-        if ctx.needs_input_grad[0]:
+        def data_gradient():
             into = _slot_target(ctx.slot, torch.empty((B, D, H, W, Cin), device="meta"))
             gxcl, _ = _wino_df_gemm(gcl, w, B, D, H, W, Cout, Cin, 1, f"winoDF dgrad {Cin}->{Cout} {D}x{H}x{W}", fl, into=into)
             if ctx.slot is not None:
                 ctx.slot.buf = gxcl
-            gx = from_cl(gxcl)
-        if ctx.needs_input_grad[1] and not gw_side:
-            gw = weight_gradient()
-        return gx, gw, None
+            return from_cl(gxcl)
+
+        want = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], False)
+        return _conv_grads(gy.device, weight, want, False, (gcl, P), weight_gradient, data_gradient)
 
 
 class _WinoConv(torch.autograd.Function):
@@ -1690,15 +1728,16 @@ def conv_flops_3x3(B, D, H, W, Cin, Cout):
 def wino_conv3d_applicable(x, weight, stride, padding, dilation):
     """Wide stride-1 3x3x3 (or 1x3x3) 'same' layers on even grids; narrow ones are memory-bound in the 8x (4x) larger
     transformed domain."""
-    k = tuple(weight.shape[2:])
-    if not (x.is_cuda and tuple(stride) == (1, 1, 1) and tuple(dilation) == (1, 1, 1) and weight.shape[0] >= 64
-            and weight.shape[1] >= 64 and weight.shape[1] % 4 == 0):
+    return _wino_applicable(x.is_cuda, x.shape, weight.shape, stride, padding, dilation)
+
+
+def _wino_applicable(is_cuda, xshape, wshape, stride, padding, dilation):
+    k = tuple(wshape[2:])
+    if k not in ((3, 3, 3), (1, 3, 3)):
         return False
-    if k == (3, 3, 3):
-        return tuple(padding) == (1, 1, 1) and all(int(n) % 2 == 0 for n in x.shape[2:])
-    if k == (1, 3, 3):
-        return tuple(padding) == (0, 1, 1) and all(int(n) % 2 == 0 for n in x.shape[3:])
-    return False
+    tiled = xshape[2:] if k[0] == 3 else xshape[3:]                 # kd = 1: the depth axis is a batch axis
+    return (is_cuda and tuple(stride) == (1, 1, 1) and tuple(dilation) == (1, 1, 1) and wshape[0] >= 64 and wshape[1] >= 64
+            and wshape[1] % 4 == 0 and tuple(padding) == (k[0] // 2, 1, 1) and all(int(n) % 2 == 0 for n in tiled))
 
 
 # -------------------------------------------------------------------------------------------------
