@@ -11,7 +11,7 @@ which is the layout the kernels read and write; nothing is permuted on the way i
 """
 import ctypes as C
 import math
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import os
 
@@ -106,13 +106,14 @@ def _conv_tag(d, role):
             f"k{d.kd}{d.kh}{d.kw} s{d.sd}{d.sh}{d.sw} d{d.dd}{d.dh}{d.dw}")
 
 
-def _conv_family(lib, d, mode):
+def _conv_family(lib, d, mode, cls=None):
     """Span family of a direct conv launch: the <= 32-channel layers on conv_taph_kernel execute 2/3 of the operator's
     multiply-adds (F(2,3) along h), on conv_tapdh_kernel 4/9 (F(2,3) along d and h), which bench.py's executed-FLOP figure
-    accounts for."""
+    accounts for.  ``cls``: the kernel class of (d, mode) where the caller knows it (else it is asked, when a timer listens)."""
     if KERNEL_TIMER is None:
         return "conv_gather"
-    return {2: "conv_tap_h", 9: "conv_tap_dh"}.get(lib.ssbev_conv_kernel_class(C.byref(d), mode), "conv_gather")
+    cls = lib.ssbev_conv_kernel_class(C.byref(d), mode) if cls is None else cls
+    return {2: "conv_tap_h", 9: "conv_tap_dh"}.get(cls, "conv_gather")
 
 
 # conv_taph_kernel runs F(2,3) along h inside the direct kernel: 2/3 of the operator's multiply-adds are executed;
@@ -568,6 +569,123 @@ def _conv_dims(xshape_cl, wshape, stride, padding, dilation, transposed, output_
     return d
 
 
+# -------------------------------------------------------------------------------------------------
+# operand plan of the fp32 direct leaf: which problem each pass of _ConvNd hands to the library
+# -------------------------------------------------------------------------------------------------
+# ONE place decides and ONE place executes, like _conv_route / _conv_run one level up.  `_conv_operands` is a pure function of
+# shapes, the geometry tuple, the module switches (TILE_HINT, PRECISION, OWN_GEMM, read at call time) and the host-only class
+# query; it touches no tensor and returns a `_ConvPlan` with the ssbev_conv_dims of each pass.  `_ConvNd` makes the plan once in
+# forward, keeps it on ctx and only executes: it pads an operand's channels up to what the pass's dims say (_pad_channels,
+# _pad_weight), launches, and crops the result back to the layer's own channel counts.  tests/test_conv_operands_snapshot.py pins
+# what reaches the C boundary for thin, padded and plain channel pairs under every switch.
+#
+# The rules, each a detail of forward or backward once and kept as found:
+#   * the kernels load their K role in float4: Cin of the forward (`kpad`) and Cout of the data gradient (`cpad`) are padded to a
+#     multiple of 4, and so is the matching axis of the weight; the direct weight gradient gets both tensors padded and its result
+#     is cropped to the parameter's shape;
+#   * the thin-side kernels (conv_thin_mfma.hip) take 1 / 2 / 4 channels against 32 as they are.  Class 4 (mode 0): the forward
+#     runs unpadded and x is SAVED unpadded, so a direct weight gradient pads x by itself (`tpad`); class 4 (mode 1): the data
+#     gradient takes gy and the weight unpadded; class 6 (mode 2): the weight gradient takes both operands unpadded ("thin").
+#     They are only asked where x was saved unpadded, and never for a transposed layer;
+#   * class 5 (forward or data gradient) runs on the thin-out entry points instead of ssbev_conv_fwd / _bwd_data;
+#   * the `fork` slot may be taken unless gx is cropped afterwards (kpad) or class 4 / 5 writes it: their kernels have no
+#     accumulating epilogue.  A slot taken on a cropped gradient would double-count or drop it silently;
+#   * a pointwise layer's weight gradient over >= 32768 rows with <= 128 channels on both sides is the skinny TN product of
+#     gemm_tn ("tn": OWN_GEMM, fp32 operands, nothing padded).
+# A pass that autograd does not want (`want`) is not planned: its dims are None and it costs no query.  The class is asked at most
+# once per distinct (dims, mode).  The switches are read HERE, when the forward runs, for the backward too.
+class _ConvPlan(NamedTuple):
+    cin: int                          # the layer's own channel counts: what gx and gw are cropped back to
+    cout: int
+    fwd: capi.ConvDims                # Cin after kpad, unpadded when class 4 takes the thin input; x is saved with fwd.Cin channels
+    fwd_class: int                    # 5: the thin-out entry points run it; 2 / 9 name the span family
+    dgrad: Optional[capi.ConvDims]    # Cout after cpad (the own dims when class 4 takes gy unpadded), Cin = fwd.Cin
+    dgrad_class: int
+    slot_ok: bool                     # the data gradient may take the `fork` slot
+    wgrad_kind: str                   # "tn" | "thin" | "direct"
+    wgrad: Optional[capi.ConvDims]    # direct: Cin after kpad / tpad, Cout after cpad; tn, thin: the own dims
+
+
+def _conv_operands(xshape_cl, wshape, geom, relu, want=(True, True)):
+    """xshape_cl = (B, Di, Hi, Wi, Cin), weight shape in the torch layout, geom = (stride, padding, dilation, transposed,
+    output_padding); want = (data gradient, weight gradient) wanted."""
+    lib = capi.load()
+    stride, padding, _, transposed, _ = geom
+    cin, cout, k = xshape_cl[-1], wshape[1 if transposed else 0], tuple(wshape[2:])
+    asked = {}
+
+    def dims(ci, co, relu=0):
+        return _conv_dims(tuple(xshape_cl[:-1]) + (ci,), ((ci, co) if transposed else (co, ci)) + k, *geom, relu=int(relu))
+
+    def cls(d, mode):
+        key = (bytes(d), mode)
+        if key not in asked:
+            asked[key] = lib.ssbev_conv_kernel_class(C.byref(d), mode)
+        return asked[key]
+
+    kpad, cpad = (-cin) % 4, (-cout) % 4
+    own = dims(cin, cout)
+    thin_in = bool(kpad) and not transposed and cls(own, 0) == 4
+    kin = cin if thin_in else cin + kpad
+    fwd = dims(kin, cout, relu)
+    unpadded = not transposed and kin == cin                 # x is saved as it came: the thin-side kernels can be asked
+    dgrad, dgrad_class, slot_ok = None, 0, False
+    if want[0]:
+        thin_d = unpadded and bool(cpad) and cls(own, 1) == 4
+        dgrad = own if thin_d else dims(kin, cout + cpad)
+        dgrad_class = cls(dgrad, 1)
+        slot_ok = kin == cin and dgrad_class not in (4, 5)
+    wgrad, wgrad_kind = None, ""
+    if want[1]:
+        if (not transposed and k == (1, 1, 1) and tuple(stride) == (1, 1, 1) and tuple(padding) == (0, 0, 0) and not kpad and not cpad
+                and wshape[0] <= 128 and wshape[1] <= 128 and own.B * own.Do * own.Ho * own.Wo >= 32768
+                and OWN_GEMM and PRECISION == "fp32"):
+            wgrad_kind, wgrad = "tn", own
+        elif unpadded and (cpad or kpad) and cls(own, 2) == 6:
+            wgrad_kind, wgrad = "thin", own
+        else:
+            wgrad_kind, wgrad = "direct", dims(cin + kpad, cout + cpad)
+    return _ConvPlan(cin, cout, fwd, cls(fwd, 0), dgrad, dgrad_class, slot_ok, wgrad_kind, wgrad)
+
+
+def _pad_channels(tcl, n):
+    """A channels-last tensor with its last axis zero-padded to ``n`` channels (the tensor itself where it has them)."""
+    return tcl if tcl.shape[-1] == n else torch.nn.functional.pad(tcl, (0, n - tcl.shape[-1]))
+
+
+def _pad_weight(w5, kn, nn, transposed):
+    """A torch-layout weight with its K-role axis (Cin: axis 1, axis 0 of a transposed layer) zero-padded to ``kn`` and its N-role
+    axis (Cout) to ``nn`` channels."""
+    ka, na = (0, 1) if transposed else (1, 0)
+    pads = [0, 0, 0, 0]                                      # F.pad counts from the last axis: (axis 1 lo, hi, axis 0 lo, hi)
+    pads[3 - 2 * ka], pads[3 - 2 * na] = kn - w5.shape[ka], nn - w5.shape[na]
+    return w5 if not any(pads) else torch.nn.functional.pad(w5, [0] * 6 + pads)
+
+
+def _masked_gradient(ctx, gy):
+    """The incoming gradient as a channels-last buffer; after a fused ReLU times [y > 0] of the saved output, in one pass."""
+    gcl = to_cl(gy)
+    return torch.ops.aten.threshold_backward(gcl, ctx.saved_tensors[2], 0.0) if ctx.relu else gcl
+
+
+def _into_slot(slot, like, d, launch):
+    """Run ``launch(gxcl)``, the data gradient of dims ``d``, into the buffer another consumer has left in ``slot`` (the kernels
+    add in their epilogue: accumulate = 1) or into a fresh tensor like ``like``, and leave the result in the slot."""
+    into = _slot_target(slot, like)
+    gxcl = into if into is not None else torch.empty_like(like)
+    d.accumulate = int(into is not None)
+    launch(gxcl)
+    d.accumulate = 0
+    if slot is not None:
+        slot.buf = gxcl
+    return gxcl
+
+
+def _bias_gradient(gcl):
+    """Column sum of a channels-last gradient, fp32."""
+    return gcl.reshape(-1, gcl.shape[-1]).sum(0, dtype=torch.float32)
+
+
 def _packed(weight5, d, mode):
     """MFMA operand layout of a weight tensor (packed on the device; a few microseconds)."""
     lib = capi.load()
@@ -621,31 +739,25 @@ class _ConvNd(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             streams.note_use(weight)
         xcl = to_cl(_f32(x, "conv"))
-        kpad = (-xcl.shape[-1]) % 4
-        w5 = weight
-        thin_in = False
-        if kpad and not transposed:   # 1..2 -> 32 channel 3x3x3 layers: conv_thinin_kernel gathers the thin side unpadded
-            d0 = _conv_dims(tuple(xcl.shape), tuple(weight.shape), stride, padding, dilation, transposed, output_padding)
-            thin_in = lib.ssbev_conv_kernel_class(C.byref(d0), 0) == 4
-        if kpad and not thin_in:   # the K-role channel count must be a multiple of 4 (float4 operand loads)
-            xcl = torch.nn.functional.pad(xcl, (0, kpad))
-            w5 = torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, 0) + ((0, 0, 0, kpad) if transposed else (0, kpad)))
-        d = _conv_dims(tuple(xcl.shape), tuple(w5.shape), stride, padding, dilation, transposed, output_padding, relu=int(relu))
+        p = _conv_operands(tuple(xcl.shape), tuple(weight.shape), (stride, padding, dilation, transposed, output_padding), relu,
+                           ctx.needs_input_grad[:2])
+        d = p.fwd
+        xcl = _pad_channels(xcl, d.Cin)
+        w5 = _pad_weight(weight.detach(), d.Cin, d.Cout, transposed)
         y = torch.empty(d.B, d.Do, d.Ho, d.Wo, d.Cout, dtype=torch.float32, device=x.device)
         b = bias.detach().contiguous() if bias is not None else None
-        fam = _conv_family(lib, d, 0)
+        fam = _conv_family(lib, d, 0, p.fwd_class)
         with _span(fam, conv_flops(d), conv_bytes(d), _conv_tag(d, "fwd"), conv_flops(d) / _EXEC_DIV[fam]):
-            if lib.ssbev_conv_kernel_class(C.byref(d), 0) == 5:
-                _thin_out_run(lib, xcl, w5.detach(), b, y, d, 0)
+            if p.fwd_class == 5:
+                _thin_out_run(lib, xcl, w5, b, y, d, 0)
             else:
-                wp = _packed(w5.detach(), d, 0)
+                wp = _packed(w5, d, 0)
                 capi.check(lib.ssbev_conv_fwd(capi.ptr(xcl), capi.ptr(wp), capi.ptr(b), capi.ptr(y), C.byref(d),
                                               capi.stream()), "ssbev_conv_fwd")
         # fused ReLU (the kernels' epilogue): backward masks the incoming gradient with the saved output's sign
         ctx.relu = bool(relu)
         ctx.save_for_backward(xcl, weight, *((y,) if relu else ()))
-        ctx.cfg = (stride, padding, dilation, transposed, output_padding, 0 if thin_in else kpad, bias is not None)
-        ctx.thin_in = thin_in
+        ctx.plan, ctx.cfg = p, (transposed, bias is not None)
         ctx.bias_leaf = bias is not None and bias.is_leaf and bias.grad is None
         return from_cl(y)
 
@@ -653,85 +765,47 @@ class _ConvNd(torch.autograd.Function):
     def backward(ctx, gy):
         lib = capi.load()
         xcl, weight = ctx.saved_tensors[:2]
-        stride, padding, dilation, transposed, output_padding, kpad, has_bias = ctx.cfg
-        args = (stride, padding, dilation, transposed, output_padding)
-        if ctx.relu:
-            ycl = ctx.saved_tensors[2]
-            gy = from_cl(torch.ops.aten.threshold_backward(to_cl(gy).contiguous(), ycl, 0.0))     # gy * [y > 0], one pass
-        gcl0 = to_cl(gy)                                    # gradient as it arrives: Cout channels
-        Cout_g = gcl0.shape[-1]
-        cpad = (-Cout_g) % 4                                # the data gradient's K role is the forward Cout: multiple of 4 ...
-        tpad = (-xcl.shape[-1]) % 4 if ctx.thin_in else 0   # ... and the weight gradient wants Cin % 4 == 0 (forward ran unpadded)
-        want_gx, want_gw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        # ... except on the thin-side kernels (conv_thin_mfma.hip), which take both tensors as they are
-        thin_d = thin_w = False
-        d0 = None
-        if not transposed and not kpad and (cpad or tpad):
-            d0 = _conv_dims(tuple(xcl.shape), tuple(weight.shape), *args)
-            thin_d = bool(cpad) and lib.ssbev_conv_kernel_class(C.byref(d0), 1) == 4
-            thin_w = lib.ssbev_conv_kernel_class(C.byref(d0), 2) == 6
-        w5 = weight.detach()
-        if kpad:
-            w5 = torch.nn.functional.pad(w5, (0, 0, 0, 0, 0, 0) + ((0, 0, 0, kpad) if transposed else (0, kpad)))
-        gcl = gcl0
-        if cpad and ((want_gx and not thin_d) or (want_gw and not thin_w)):
-            gcl = torch.nn.functional.pad(gcl0, (0, cpad))
-            w5 = torch.nn.functional.pad(w5, (0, 0, 0, 0, 0, 0) + ((0, cpad) if transposed else (0, 0, 0, cpad)))
-        elif cpad:
-            w5 = None                                       # nobody needs the padded operands
-        d = _conv_dims(tuple(xcl.shape), tuple(w5.shape), *args) if w5 is not None else d0
+        p, (transposed, has_bias) = ctx.plan, ctx.cfg
+        gcl0 = _masked_gradient(ctx, gy)                    # gradient as it arrives: Cout channels
+        # ... padded ONCE if a wanted pass takes it padded (the thin-side kernels and the TN product take it as it is)
+        want = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2])
+        gcl = _pad_channels(gcl0, max([p.cout] + [d.Cout for d, on in zip((p.dgrad, p.wgrad), want) if on]))
+        gy_of = lambda d: gcl if d.Cout == gcl.shape[-1] else gcl0
 
         def weight_gradient():
-            pointwise = (not transposed and tuple(weight.shape[2:]) == (1, 1, 1) and stride == (1, 1, 1) and padding == (0, 0, 0)
-                         and not kpad and not cpad and not tpad and weight.shape[0] <= 128 and weight.shape[1] <= 128
-                         and gcl0.numel() // Cout_g >= 32768)
-            if pointwise and OWN_GEMM and PRECISION == "fp32":
+            d = p.wgrad
+            if p.wgrad_kind == "tn":
                 # 1x1x1 layers on the cost volume: gw[co][ci] = sum_rows gy[row][co] x[row][ci], an HBM-streaming skinny TN product
                 with _span("conv_wgrad", conv_flops(d), conv_bytes(d), _conv_tag(d, "wgrad")):
-                    gw = gemm_tn(gcl0.reshape(-1, Cout_g), xcl.reshape(-1, xcl.shape[-1])).view_as(weight)
-            else:
-                if thin_w:
-                    xw, gw_src, dw, wshape = xcl, gcl0, d0, tuple(weight.shape)
-                else:
-                    xw, gw_src, dw, wshape = xcl, gcl, d, tuple(w5.shape)
-                    if tpad:      # forward ran on the unpadded thin input (conv_thinin_kernel)
-                        xw = torch.nn.functional.pad(xcl, (0, tpad))
-                        wshape = (wshape[0], wshape[1] + tpad) + wshape[2:]
-                        dw = _conv_dims(tuple(xw.shape), wshape, *args)
-                gwp = torch.empty(wshape, dtype=torch.float32, device=gy.device)
-                ws = _ws(lib.ssbev_conv_bwd_weight_workspace(C.byref(dw)), gy.device)
-                with _span("conv_wgrad", conv_flops(dw), conv_bytes(dw), _conv_tag(dw, "wgrad")):
-                    capi.check(lib.ssbev_conv_bwd_weight(capi.ptr(xw), capi.ptr(gw_src), capi.ptr(gwp), C.byref(dw),
-                                                         capi.ptr(ws), ws.numel(), capi.stream()),
-                               "ssbev_conv_bwd_weight")
-                gw = gwp if tuple(wshape) == tuple(weight.shape) else gwp[: weight.shape[0], : weight.shape[1]].contiguous()
-            return gw
+                    return gemm_tn(gcl0.reshape(-1, p.cout), xcl.reshape(-1, p.cin)).view_as(weight)
+            xw = _pad_channels(xcl, d.Cin)                  # (a copy only after a forward on the unpadded thin input)
+            gwp = torch.empty(((d.Cin, d.Cout) if transposed else (d.Cout, d.Cin)) + tuple(weight.shape[2:]), dtype=torch.float32,
+                              device=gy.device)
+            ws = _ws(lib.ssbev_conv_bwd_weight_workspace(C.byref(d)), gy.device)
+            with _span("conv_wgrad", conv_flops(d), conv_bytes(d), _conv_tag(d, "wgrad")):
+                capi.check(lib.ssbev_conv_bwd_weight(capi.ptr(xw), capi.ptr(gy_of(d)), capi.ptr(gwp), C.byref(d),
+                                                     capi.ptr(ws), ws.numel(), capi.stream()),
+                           "ssbev_conv_bwd_weight")
+            return gwp if gwp.shape == weight.shape else gwp[: weight.shape[0], : weight.shape[1]].contiguous()
 
         def data_gradient():
-            dd, gdl, wd = (d0, gcl0, weight.detach()) if thin_d else (d, gcl, w5)
-            slot = ctx.slot if (not kpad and not thin_d and lib.ssbev_conv_kernel_class(C.byref(dd), 1) not in (4, 5)) else None
-            into = _slot_target(slot, xcl)
-            if into is not None:          # another consumer's gradient is already there: add to it in the kernel's epilogue
-                dd.accumulate = 1
-            gxcl = into if into is not None else torch.empty_like(xcl)
-            fam = _conv_family(lib, dd, 1)
-            with _span(fam, conv_flops(dd), conv_bytes(dd), _conv_tag(dd, "dgrad"), conv_flops(dd) / _EXEC_DIV[fam]):
-                if lib.ssbev_conv_kernel_class(C.byref(dd), 1) == 5:
-                    _thin_out_run(lib, gdl, wd, None, gxcl, dd, 1)
-                else:
-                    wpt = _packed(wd, dd, 1)
-                    capi.check(lib.ssbev_conv_bwd_data(capi.ptr(gdl), capi.ptr(wpt), capi.ptr(gxcl), C.byref(dd),
-                                                       capi.stream()), "ssbev_conv_bwd_data")
-            dd.accumulate = 0
-            if slot is not None:
-                slot.buf = gxcl
-            if kpad:
-                gxcl = gxcl[..., : xcl.shape[-1] - kpad]
-            return from_cl(gxcl)
+            d = p.dgrad
+            gdl, wd = gy_of(d), _pad_weight(weight.detach(), d.Cin, d.Cout, transposed)
 
-        want = (want_gx, want_gw, has_bias and ctx.needs_input_grad[2])
+            def launch(gxcl):
+                fam = _conv_family(lib, d, 1, None if d.accumulate else p.dgrad_class)     # (the class was asked without accumulate)
+                with _span(fam, conv_flops(d), conv_bytes(d), _conv_tag(d, "dgrad"), conv_flops(d) / _EXEC_DIV[fam]):
+                    if p.dgrad_class == 5:
+                        _thin_out_run(lib, gdl, wd, None, gxcl, d, 1)
+                    else:
+                        wpt = _packed(wd, d, 1)
+                        capi.check(lib.ssbev_conv_bwd_data(capi.ptr(gdl), capi.ptr(wpt), capi.ptr(gxcl), C.byref(d),
+                                                           capi.stream()), "ssbev_conv_bwd_data")
+            gxcl = _into_slot(ctx.slot if p.slot_ok else None, xcl, d, launch)
+            return from_cl(gxcl if d.Cin == p.cin else gxcl[..., : p.cin])
+
         return _conv_grads(gy.device, weight, want, ctx.bias_leaf, (xcl, gcl0, gcl), weight_gradient, data_gradient,
-                           lambda: gcl0.reshape(-1, Cout_g).sum(0)) + (None,) * 7
+                           lambda: _bias_gradient(gcl0)) + (None,) * 7
 
 
 def _conv16_family(lib, d, mode):
@@ -772,12 +846,9 @@ class _ConvNd16(torch.autograd.Function):
         lib = capi.load()
         xcl, weight = ctx.saved_tensors[:2]
         stride, padding, dilation, transposed, output_padding, has_bias = ctx.cfg
-        gcl = to_cl(gy)
-        if ctx.relu:
-            gcl = torch.ops.aten.threshold_backward(gcl.contiguous(), ctx.saved_tensors[2], 0.0)
+        gcl = _masked_gradient(ctx, gy)
         if gcl.dtype != torch.bfloat16:
             gcl = gcl.to(torch.bfloat16)
-        Cout_g = gcl.shape[-1]
         d = _conv_dims(tuple(xcl.shape), tuple(weight.shape), stride, padding, dilation, transposed, output_padding)
         d.precision = 2
 
@@ -795,22 +866,16 @@ class _ConvNd16(torch.autograd.Function):
             return gwp
 
         def data_gradient():
-            into = _slot_target(ctx.slot, xcl)
-            if into is not None:
-                d.accumulate = 1
-            gxcl = into if into is not None else torch.empty_like(xcl)
-            with _span(_conv16_family(lib, d, 1), conv_flops(d), conv_bytes(d) / 2.0, _conv_tag(d, "dgrad")):
-                wpt = _packed(weight.detach(), d, 1)
-                capi.check(lib.ssbev_conv_bwd_data_bf16(capi.ptr(gcl), capi.ptr(wpt), capi.ptr(gxcl), C.byref(d), capi.stream()),
-                           "ssbev_conv_bwd_data_bf16")
-            d.accumulate = 0
-            if ctx.slot is not None:
-                ctx.slot.buf = gxcl
-            return from_cl(gxcl)
+            def launch(gxcl):
+                with _span(_conv16_family(lib, d, 1), conv_flops(d), conv_bytes(d) / 2.0, _conv_tag(d, "dgrad")):
+                    wpt = _packed(weight.detach(), d, 1)
+                    capi.check(lib.ssbev_conv_bwd_data_bf16(capi.ptr(gcl), capi.ptr(wpt), capi.ptr(gxcl), C.byref(d), capi.stream()),
+                               "ssbev_conv_bwd_data_bf16")
+            return from_cl(_into_slot(ctx.slot, xcl, d, launch))
 
         want = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2])
         return _conv_grads(gy.device, weight, want, ctx.bias_leaf, (xcl, gcl), weight_gradient, data_gradient,
-                           lambda: gcl.reshape(-1, Cout_g).sum(0, dtype=torch.float32)) + (None,) * 8
+                           lambda: _bias_gradient(gcl)) + (None,) * 8
 
 
 # bf16 storage mode: the wide stride-1 3x3x3 layers on grids with W % 16 == 0 (voxel encoder level 0, head conv, the 64 -> 64

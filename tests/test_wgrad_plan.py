@@ -10,7 +10,7 @@ import ctypes as C
 import pytest
 
 import wgrad_cases as T
-from stereoscene_amd import capi
+from stereoscene_amd import capi, functional as F
 
 IDS = [c.id for c in T.CASES]
 
@@ -108,6 +108,14 @@ def test_padded_problems_of_the_wrappers_keep_their_kind():
         assert (cin, cout) == (c.Cin + (-c.Cin) % 4, c.Cout + (-c.Cout) % 4)
         plan = T.query(T.dims(c._replace(Cin=cin, Cout=cout)))
         assert (T.KINDS[plan["kind"]], plan["two_stage"]) == (kind, two_stage), (cid, plan)
+        # ... and the wrapper's operand plan hands exactly these channel counts to ssbev_conv_bwd_weight
+        saved = F.TILE_HINT
+        F.TILE_HINT = c.hint
+        try:
+            p = F._conv_operands((c.B,) + tuple(c.grid) + (c.Cin,), T.wshape(c), (c.s, c.p, c.dl, bool(c.tr), c.op), False)
+        finally:
+            F.TILE_HINT = saved
+        assert (p.wgrad_kind, p.wgrad.Cin, p.wgrad.Cout) == ("direct", cin, cout), (cid, p)
 
 
 def test_bf16_storage_is_named_and_bad_arguments_are_refused():
