@@ -1070,6 +1070,23 @@ int ssbev_wino_dgemm(const float* P, const float* Wp, float* Mo, const ssbev_win
 /* Batched frequency GEMM of the plain 3-D pipeline: Cm[xi][T][N] = A[xi][T][K] x U[xi][K][N] for the 64 frequencies, A
  * streamed through LDS once, U in the ssbev_wino_dgemm_pack layout. */
 int ssbev_wino_bgemm(const float* A, const float* Wp, float* Cm, int64_t T, int K, int N, ssbev_stream_t stream);
+/* Host-side plan query (since ssbev_version() 124; no device work): the launch geometry of ssbev_wino_bgemm(T, K, N) (b_ group,
+ * filled when T > 0) and of ssbev_wino_dgemm(d, N) (d_ group, filled when d is not NULL), from the plan functions the two
+ * launchers themselves read; the group that is not asked for is zero.  SSBEV_EINVAL for a NULL `out`, when neither group is
+ * asked for, and for arguments the launcher of a requested group refuses. */
+typedef struct {
+  int b_nt;                 /* wino_bgemm_kernel<NT>: 32-column tiles per wave */
+  int b_ycols;              /* grid y: column groups of 4 NT 32 columns */
+  int b_gx;                 /* grid x: persistent workgroups per (frequency, column group) */
+  int b_nstage;             /* 64-column k-stages per row block */
+  int64_t b_nrb, b_rb_per;  /* 64-row blocks, and row blocks per workgroup (workgroup x owns [x rb_per, (x + 1) rb_per)) */
+  int d_mt, d_nt;           /* wino_dgemm_kernel<MT, NT> */
+  int d_tgroups;            /* groups of 32 MT (h, w)-tiles per plane; a workgroup's four waves take four consecutive groups */
+  int d_grid_x, d_grid_y, d_grid_z;
+  int d_Q;                  /* k-steps of 8 channels */
+  int d_CoutPad;            /* N rounded up to 32: the column stride of the packed weights */
+} ssbev_wino_gemm_plan;
+int ssbev_wino_gemm_plan_query(int64_t T, int K, int N, const ssbev_wino_dims* d, ssbev_wino_gemm_plan* out);
 
 /* ------------------------------------------------------------------------------------------
  * Plain fp32 GEMMs on the matrix cores (csrc/gemm.hip): the layers that are matrix products in the channels-last layout

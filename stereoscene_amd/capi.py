@@ -157,6 +157,12 @@ class Wino43DfPlan(C.Structure):
                 ("w_grid", C.c_int64), ("w_lds_bytes", C.c_size_t), ("w_workspace", C.c_size_t)]
 
 
+class WinoGemmPlan(C.Structure):
+    _fields_ = [("b_nt", C.c_int), ("b_ycols", C.c_int), ("b_gx", C.c_int), ("b_nstage", C.c_int), ("b_nrb", C.c_int64),
+                ("b_rb_per", C.c_int64)] + \
+        [(n, C.c_int) for n in ("d_mt", "d_nt", "d_tgroups", "d_grid_x", "d_grid_y", "d_grid_z", "d_Q", "d_CoutPad")]
+
+
 class ConvBf16Plan(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("kernel", "mt", "nt", "bm", "bn", "bkc", "ntl", "nth", "ntw", "ntn", "nseg", "gpc",
                                        "mq", "mp", "th", "tw", "chunk", "nchunks", "narrow", "tpc", "ncqt")] + \
@@ -291,6 +297,7 @@ SIGNATURES = {
     "ssbev_wino_dgemm_pack": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ssbev_wino_dgemm": (C.c_int, [_P, _P, _P, C.POINTER(WinoDims), C.c_int, _P]),
     "ssbev_wino_bgemm": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, _P]),
+    "ssbev_wino_gemm_plan_query": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.POINTER(WinoDims), C.POINTER(WinoGemmPlan)]),
     "ssbev_gemm_d2s_rowoff": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "ssbev_gemm_nn_workspace": (C.c_size_t, [C.POINTER(GemmDims)]),
     "ssbev_gemm_nt_workspace": (C.c_size_t, [C.POINTER(GemmDims)]),

@@ -29,7 +29,7 @@ const char* ssbev_env(const char* name) {
 }
 
 extern "C" {
-int ssbev_version(void) { return 123; /* 0.1.23: + ssbev_conv_wgrad_plan_query */ }
+int ssbev_version(void) { return 124; /* 0.1.24: + ssbev_wino_gemm_plan_query */ }
 const char* ssbev_build_arch(void) { return "gfx950"; }
 
 // Forget every switch read so far: the next use of a name reads the environment again.  (Switches that a launch helper folded

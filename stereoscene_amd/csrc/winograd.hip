@@ -816,12 +816,16 @@ typedef float wf32x16 __attribute__((ext_vector_type(16)));
 
 struct WinoGemmGeom { int B, D, Thw, Cin, Cout, CoutPad; };
 
+// launch geometry that the kernels, the launchers and ssbev_wino_gemm_plan_query all read
+__host__ __device__ constexpr int wino_gemm_q(int K) { return (K + 7) >> 3; }                          // k-steps of 8 channels
+__host__ __device__ constexpr int wino_dgemm_tgroups(int Thw, int mt) { return (Thw + 32 * mt - 1) / (32 * mt); }
+
 template <int MT, int NT>
 __global__ void __launch_bounds__(256)
 wino_dgemm_kernel(const float* __restrict__ P, const float* __restrict__ Wp, float* __restrict__ Mo, WinoGemmGeom g) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 31, lk = lane >> 5;
-  const int tgroups = (g.Thw + 32 * MT - 1) / (32 * MT), tg4 = ((tgroups + 3) >> 2) << 2;
+  const int tgroups = wino_dgemm_tgroups(g.Thw, MT), tg4 = ((tgroups + 3) >> 2) << 2;
   // blockIdx.x: (b, depth tile, 4 tile groups) ; blockIdx.y: column group ; blockIdx.z: xi_hw
   const int tg = (blockIdx.x * 4 + wave) % tg4;
   const int bi = (blockIdx.x * 4 + wave) / tg4;
@@ -849,7 +853,7 @@ wino_dgemm_kernel(const float* __restrict__ P, const float* __restrict__ Wp, flo
       for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[f][mt][nt][r] = 0.0f;
-  const int Q = (g.Cin + 7) >> 3;
+  const int Q = wino_gemm_q(g.Cin);
   const size_t fstride = (size_t)Q * 2 * g.CoutPad * 4;               // floats per frequency in Wp
   const float* wl = Wp + ((size_t)lk * g.CoutPad + n0 + li) * 4 + (size_t)xhw * fstride;
   for (int q = 0; q < Q; ++q) {
@@ -916,6 +920,9 @@ wino_dgemm_kernel(const float* __restrict__ P, const float* __restrict__ Wp, flo
 struct WinoBgemmGeom { long T; int K, N, NPad; };
 
 constexpr int kBgBM = 64, kBgBK = 64, kBgStages = 3;
+__host__ __device__ constexpr long wino_bgemm_nrb(long T) { return (T + kBgBM - 1) / kBgBM; }           // 64-row blocks
+__host__ __device__ constexpr int wino_bgemm_nstage(int K) { return (K + kBgBK - 1) / kBgBK; }          // k-stages per row block
+__host__ __device__ constexpr long wino_bgemm_rb_per(long nrb, long gx) { return (nrb + gx - 1) / gx; } // row blocks per workgroup
 
 template <int NT>
 __global__ void __launch_bounds__(256)
@@ -928,13 +935,13 @@ wino_bgemm_kernel(const float* __restrict__ A, const float* __restrict__ Wp, flo
   const bool col_active = n0 < g.N;
   const float* Ax = A + (long)xi * g.T * g.K;
   float* Cx = Cm + (long)xi * g.T * g.N;
-  const int Q = (g.K + 7) >> 3, nstage = (g.K + kBgBK - 1) / kBgBK;
+  const int Q = wino_gemm_q(g.K), nstage = wino_bgemm_nstage(g.K);
   const size_t fstride = (size_t)Q * 2 * g.NPad * 4;
   const float* wl = Wp + (size_t)xi * fstride + ((size_t)lk * g.NPad + n0 + li) * 4;
   // persistent walk: this workgroup owns row blocks rb0, rb0+1, ..., the LDS ring runs across row-block boundaries so
   // that the loads of the next block are in flight while this one is multiplied
-  const long nrb = (g.T + kBgBM - 1) / kBgBM;
-  const long rb_per = (nrb + gridDim.x - 1) / gridDim.x;
+  const long nrb = wino_bgemm_nrb(g.T);
+  const long rb_per = wino_bgemm_rb_per(nrb, gridDim.x);
   const long rb_begin = (long)blockIdx.x * rb_per, rb_end = min(nrb, rb_begin + rb_per);
   const long total = (rb_end - rb_begin) * nstage;       // flat (row block, k stage) sequence
   if (total <= 0) return;
@@ -1065,6 +1072,41 @@ bool wino_ok(const ssbev_wino_dims* d) {
   return d && d->B > 0 && d->C > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->D % 2 == 0 && d->H % 2 == 0 && d->W % 2 == 0 && d->dil <= 1;
 }
 
+// ---- launch plans of the two frequency GEMMs: the launchers and ssbev_wino_gemm_plan_query read these and nothing else ----
+bool wino_dgemm_plan(const ssbev_wino_dims* d, int N, ssbev_wino_gemm_plan& p) {
+  if (!wino_ok(d) || N <= 0 || d->C % 4 != 0) return false;
+  // tiling: env SSBEV_WINO_TILE = MT*10 + NT (tuning builds), default <1,2> (two to three waves per SIMD)
+  static const int forced = [] { const char* e = ssbev_tune("SSBEV_WINO_TILE"); return e ? atoi(e) : 0; }();
+  int mt = 1, nt = 2;
+  if (forced) { mt = forced / 10; nt = forced % 10; }
+  const int inst = mt * 10 + nt;
+  if (inst != 14 && inst != 13 && inst != 12 && inst != 22 && inst != 21 && inst != 11) return false;
+  const int Thw = (d->H / 2) * (d->W / 2);
+  p.d_mt = mt; p.d_nt = nt;
+  p.d_tgroups = wino_dgemm_tgroups(Thw, mt);
+  const int tg4 = (p.d_tgroups + 3) >> 2;                                 // workgroups of four waves per (b, depth tile)
+  p.d_grid_x = (int)((long)d->B * (d->D / 2) * tg4);
+  p.d_grid_y = (int)cdiv(N, nt * 32);
+  p.d_grid_z = 16;
+  p.d_Q = wino_gemm_q(d->C);
+  p.d_CoutPad = (N + 31) & ~31;
+  return true;
+}
+
+bool wino_bgemm_plan(int64_t T, int K, int N, ssbev_wino_gemm_plan& p) {
+  if (T <= 0 || K <= 0 || N <= 0 || K % 4 != 0) return false;
+  p.b_nt = N > 128 ? 2 : 1;
+  // persistent workgroups: ~3 per CU over the 64 frequencies and column groups, each walking >= 4 row blocks
+  p.b_nrb = wino_bgemm_nrb((long)T);
+  p.b_ycols = (int)cdiv(N, 4 * p.b_nt * 32);
+  long gx = std::max(1L, (768L + 64 * p.b_ycols - 1) / (64 * p.b_ycols));
+  gx = std::min(gx, std::max(1L, (long)p.b_nrb / 4));
+  p.b_gx = (int)gx;
+  p.b_nstage = wino_bgemm_nstage(K);
+  p.b_rb_per = wino_bgemm_rb_per((long)p.b_nrb, gx);
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1144,17 +1186,13 @@ int ssbev_wino_dgemm_pack(const float* w, float* Wp, int Cout, int Cin, int mode
 
 // P [16][B*D*Thw][K] (hw-transformed input), Wp from ssbev_wino_dgemm_pack, Mo [16][B*D*Thw][N]; d->C = K, N given
 int ssbev_wino_dgemm(const float* P, const float* Wp, float* Mo, const ssbev_wino_dims* d, int N, ssbev_stream_t stream) {
-  if (!wino_ok(d) || !P || !Wp || !Mo || N <= 0 || d->C % 4 != 0) return SSBEV_EINVAL;
-  const WinoGemmGeom g{d->B, d->D, (d->H / 2) * (d->W / 2), d->C, N, (N + 31) & ~31};
-  // tiling: env SSBEV_WINO_TILE = MT*10 + NT (tuning), default <1,2> (two to three waves per SIMD)
-  static const int forced = [] { const char* e = ssbev_tune("SSBEV_WINO_TILE"); return e ? atoi(e) : 0; }();
-  int mt = 1, nt = 2;
-  if (forced) { mt = forced / 10; nt = forced % 10; }
-  const int tgroups = (g.Thw + 32 * mt - 1) / (32 * mt), tg4 = (tgroups + 3) >> 2;
-  dim3 grid((unsigned)((long)g.B * (g.D / 2) * tg4), cdiv(N, nt * 32), 16), block(256);
+  ssbev_wino_gemm_plan p{};
+  if (!P || !Wp || !Mo || !wino_dgemm_plan(d, N, p)) return SSBEV_EINVAL;
+  const WinoGemmGeom g{d->B, d->D, (d->H / 2) * (d->W / 2), d->C, N, p.d_CoutPad};
+  dim3 grid((unsigned)p.d_grid_x, (unsigned)p.d_grid_y, (unsigned)p.d_grid_z), block(256);
   hipStream_t st = as_stream(stream);
 #define SSBEV_WG_LAUNCH(M_, N_) hipLaunchKernelGGL((wino_dgemm_kernel<M_, N_>), grid, block, 0, st, P, Wp, Mo, g)
-  switch (mt * 10 + nt) {
+  switch (p.d_mt * 10 + p.d_nt) {
     case 14: SSBEV_WG_LAUNCH(1, 4); break;
     case 13: SSBEV_WG_LAUNCH(1, 3); break;
     case 12: SSBEV_WG_LAUNCH(1, 2); break;
@@ -1169,20 +1207,24 @@ int ssbev_wino_dgemm(const float* P, const float* Wp, float* Mo, const ssbev_win
 
 // A [64][T][K], Wp = ssbev_wino_dgemm_pack(...) ([64][K/8][2][NPad][4]), Cm [64][T][N]
 int ssbev_wino_bgemm(const float* A, const float* Wp, float* Cm, int64_t T, int K, int N, ssbev_stream_t stream) {
-  if (!A || !Wp || !Cm || T <= 0 || K <= 0 || N <= 0 || K % 4 != 0) return SSBEV_EINVAL;
+  ssbev_wino_gemm_plan p{};
+  if (!A || !Wp || !Cm || !wino_bgemm_plan(T, K, N, p)) return SSBEV_EINVAL;
   const WinoBgemmGeom g{(long)T, K, N, (N + 31) & ~31};
-  const int nt = N > 128 ? 2 : 1;
-  // persistent workgroups: ~3 per CU over the 64 frequencies and column groups, each walking >= 4 row blocks
-  const long nrb = ((long)T + kBgBM - 1) / kBgBM;
-  const int ycols = cdiv(N, 4 * nt * 32);
-  long gx = std::max(1L, (768L + 64 * ycols - 1) / (64 * ycols));
-  gx = std::min(gx, std::max(1L, nrb / 4));
-  dim3 grid((unsigned)gx, ycols, 64), block(256);
+  dim3 grid((unsigned)p.b_gx, (unsigned)p.b_ycols, 64), block(256);
   const size_t lds = (size_t)kBgStages * kBgBM * kBgBK * sizeof(float);
   hipStream_t st = as_stream(stream);
-  if (nt == 2) hipLaunchKernelGGL(wino_bgemm_kernel<2>, grid, block, lds, st, A, Wp, Cm, g);
+  if (p.b_nt == 2) hipLaunchKernelGGL(wino_bgemm_kernel<2>, grid, block, lds, st, A, Wp, Cm, g);
   else hipLaunchKernelGGL(wino_bgemm_kernel<1>, grid, block, lds, st, A, Wp, Cm, g);
   return ssbev_launch_status();
+}
+
+int ssbev_wino_gemm_plan_query(int64_t T, int K, int N, const ssbev_wino_dims* d, ssbev_wino_gemm_plan* out) {
+  if (!out || (T <= 0 && !d)) return SSBEV_EINVAL;
+  ssbev_wino_gemm_plan p{};
+  if (T > 0 && !wino_bgemm_plan(T, K, N, p)) return SSBEV_EINVAL;
+  if (d && !wino_dgemm_plan(d, N, p)) return SSBEV_EINVAL;
+  *out = p;
+  return SSBEV_OK;
 }
 
 SSBEV_WINO2D_DIL_ENTRY(ssbev_wino2d_input_transform, wino2d_input_kernel, 0)
